@@ -23,9 +23,15 @@ Workloads (``--workload``):
                      dd8192 at 8 GPUs): overlapped-halo decomposition, halo refresh over RCCL every S steps; "scaling":
                      "strong".  ddx<N>: the exact interface exchange after every sweep (the scheme for stiff steps).
 
+A plain run sets up, warms up, times exactly `--steps` steps and prints the line (`value`, `ms_per_step`, ...).  Every
+other figure takes runs of its own and is measured only with `--full`: `roofline` (the dominant kernel timed with HIP
+events) and `hbm_frac_of_step`, the `sustained` window, `cpu_baseline`, and the multi-GPU sub-records below.
+`--dump-outputs DIR` writes what the last timed step left in the workload's state as DIR/<name>.npy (fp64; a fixed
+seeded sample of columns where the arrays are larger than the budget; rank 0's share with N > 1 ranks).
+
 Multi-GPU (the driver's `--gpus N`, default workload): the headline value stays the same workload per GPU as at N = 1
-(independent 4096^2 fields, ensemble sharding, no data-path collective -> "scaling": "weak"), and the SAME JSON line
-carries two sub-records measured in the same run:
+(independent 4096^2 fields, ensemble sharding, no data-path collective -> "scaling": "weak"); with `--full` the SAME JSON
+line carries two sub-records measured in the same run:
   "strong"    dd8192 over the N ranks (north_star: >= 6x at 8 GPUs): value, ms/step, the 1-rank time of the same 8192^2
               problem measured on rank 0 in this run, the speed-up against it, and the share of the halo exchanges;
   "ensemble"  BASELINE configs[3]: 64 N independent 256^2 MKID members, NE = 12 full physics, 64 per GPU.
@@ -49,6 +55,8 @@ for _p in (str(ROOT), str(ROOT / "quasiparticle-physics-simulation_amd")):
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level parameters)
 FP64_VECTOR_PEAK_TFLOPS = 78.6  # half of the 157.3 TF fp32 vector peak
+DUMP_MAX_VALUES = 1 << 22       # --dump-outputs: at most 4 Mi fp64 values (32 MiB) over all arrays
+DUMP_SEED = 0
 
 
 def parse_args():
@@ -57,19 +65,29 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="adi4096")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the figures that take runs of their own: roofline, sustained window, CPU baseline, "
+                         "N > 1 sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", type=Path, default=None,
+                    help="write the state after the last timed step as DIR/<name>.npy (fp64, seeded sample if large)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-size", type=int, default=512, help="grid edge of the bounded CPU-baseline sample")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed even with one rank")
-    ap.add_argument("--no-subrecords", action="store_true", help="N > 1: skip the strong-scaling / ensemble sub-records")
+    ap.add_argument("--no-subrecords", action="store_true",
+                    help="with --full, N > 1: skip the strong-scaling / ensemble sub-records")
     ap.add_argument("--force-subrecords", action="store_true",
-                    help="emit the sub-records with one rank too (with --force-dist: rehearsal of the N > 1 code path)")
+                    help="with --full: emit the sub-records with one rank too (with --force-dist: rehearsal of the N > 1 "
+                         "code path)")
     ap.add_argument("--strong-size", type=int, default=8192, help="grid edge of the strong-scaling sub-record")
     ap.add_argument("--subrecord-timeout", type=float, default=420.0,
                     help="seconds after which unfinished N > 1 sub-records are reported as errors, the line printed and "
                          "every rank exits with status 3")
     ap.add_argument("--sustained-seconds", type=float, default=0.5,
-                    help="pre-spin and window length of the `sustained` sub-record (0 disables it)")
-    return ap.parse_args()
+                    help="with --full: pre-spin and window length of the `sustained` sub-record (0 disables it)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def full_rectangle_problem(N: int):
@@ -320,6 +338,38 @@ def ensemble_record(args, dev, world: int, stage: dict | None = None) -> dict:
             "ms_per_step": 1e3 * elapsed / steps, "pixel_steps_per_s": wl.npix * world * steps / elapsed}
 
 
+def workload_outputs(wl) -> dict:
+    """The device arrays a caller of the timed path holds after its last step: the field of the diffusion workloads, the
+    quasiparticle and phonon planes of the coupled ones (this rank's block where the grid is decomposed)."""
+    if getattr(wl, "coupled", False):
+        wl = wl.inner
+    if hasattr(wl, "phonon"):
+        return {"qp_state": wl.state, "phonon": wl.phonon}
+    if hasattr(wl, "block"):
+        return {"field": wl.block.u}
+    if hasattr(wl, "be"):
+        return {"field": wl.be.u}
+    return {"field": wl.u}
+
+
+def dump_outputs(wl, out_dir: Path) -> None:
+    """Each output as out_dir/<name>.npy, fp64, shape [rows, columns] (fields or energy bins x cells).  Where the arrays hold
+    more than DUMP_MAX_VALUES values, all rows are kept at a sorted, seeded sample of columns (cells), the same for every
+    array of one size, so two runs with the same arguments write the same positions."""
+    import torch
+    arrays = {k: v.reshape(v.shape[0], -1) for k, v in workload_outputs(wl).items()}
+    sample = None
+    if sum(a.numel() for a in arrays.values()) > DUMP_MAX_VALUES:
+        sample = max(1, DUMP_MAX_VALUES // sum(a.shape[0] for a in arrays.values()))
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        cols = a.shape[1]
+        if sample is not None and cols > sample:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(cols, size=sample, replace=False))
+            a = a[:, torch.as_tensor(idx, device=a.device)]
+        np.save(out_dir / f"{name}.npy", a.detach().cpu().numpy().astype(np.float64, copy=False))
+
+
 _RESULT_FD = None
 
 
@@ -376,9 +426,9 @@ def main():
     if args.warmup > 0:
         wl.run(args.warmup)
     elapsed = timed_steps(wl, args.steps, dev, use_dist)     # exactly `steps` steps of the hot path, enqueued back to back
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(wl, args.dump_outputs)                   # before anything else advances the state
 
-    # per-kernel timing of the dominant kernel with HIP events on the launch stream (same inputs, same loop)
-    roof = wl.roofline(max(5, min(args.steps, 20)))
     strong = getattr(wl, "scaling", "weak") == "strong"
     value = wl.cell_updates_per_step * world * args.steps / elapsed
     result = {
@@ -392,17 +442,21 @@ def main():
                                    f"domain decomposition over {world} GPUs (RCCL point-to-point halo refresh)" if strong
                                    else f"independent problems x{world} (ensemble sharding, no collective)"),
                    "path": wl.path},
-        "roofline": roof,
-        "hbm_frac_of_step": (wl.bytes_per_step * args.steps / elapsed / 1e9) / HBM_PEAK_GBS,
         "build": build,
     }
-    if args.sustained_seconds > 0:
-        result["sustained"] = sustained_record(args, wl, dev, use_dist, world, 1e3 * elapsed / args.steps)
+    if args.full:
+        # per-kernel timing of the dominant kernel with HIP events on the launch stream (same inputs, same loop); the
+        # cn<N> roofline also sets the byte model that hbm_frac_of_step uses
+        result["roofline"] = wl.roofline(max(5, min(args.steps, 20)))
+        result["hbm_frac_of_step"] = (wl.bytes_per_step * args.steps / elapsed / 1e9) / HBM_PEAK_GBS
+        if args.sustained_seconds > 0:
+            result["sustained"] = sustained_record(args, wl, dev, use_dist, world, 1e3 * elapsed / args.steps)
     if hasattr(wl, "coll_bytes_per_call"):
         result["pixel_steps_per_s"] = wl.npix * world * args.steps / elapsed
     del wl
     torch.cuda.empty_cache()
-    if (world > 1 or (args.force_subrecords and use_dist)) and not args.no_subrecords and args.workload == "adi4096":
+    if (args.full and (world > 1 or (args.force_subrecords and use_dist)) and not args.no_subrecords
+            and args.workload == "adi4096"):
         # north_star's two multi-GPU figures, measured in the same run and reported next to the weak-scaling headline
         # The headline above is complete at this point; the sub-records must not be able to lose it.  An exception in
         # one becomes its "error" field, and if a rank gets stuck in them (a peer died, a collective that never returns)
@@ -453,7 +507,7 @@ def main():
         if printed.is_set():              # the watchdog fired between the last record and cancel()
             os._exit(3)
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (rank 0 would hold the others up)
+        if args.full and not args.no_cpu_baseline and world == 1:   # at N = 1 only (rank 0 would hold the others up)
             result["cpu_baseline"] = cpu_baseline(args, args.workload)
         _emit(result)
     if use_dist:

@@ -5,7 +5,7 @@ out=gpurun_out/onepass; mkdir -p $out
 if [ "$1" = test ]; then
   timeout -k 10 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_configs.py -m gpu -x -q > $out/pytest.log 2>&1; echo "pytest rc=$?"; tail -n 3 $out/pytest.log
 fi
-run() { tag=$1; shift; env "$@" timeout -k 10 300 python bench.py --workload coupled1024ne50 --steps 10 --warmup 3 --no-cpu-baseline --sustained-seconds 0 > $out/bench_$tag.json 2> $out/bench_$tag.err
+run() { tag=$1; shift; env "$@" timeout -k 10 300 python bench.py --full --workload coupled1024ne50 --steps 10 --warmup 3 --no-cpu-baseline --sustained-seconds 0 > $out/bench_$tag.json 2> $out/bench_$tag.err
   python - $out/bench_$tag.json $tag <<'PY'
 import json,sys
 try:

@@ -3,7 +3,7 @@
 out=gpurun_out/onepass_ne; mkdir -p $out
 timeout -k 10 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_configs.py -m gpu -x -q > $out/pytest.log 2>&1; echo "pytest rc=$?"; tail -n 3 $out/pytest.log
 for ne in 32 40 50; do for op in 0 1; do
-  QPSIM_COLL_ONEPASS=$op timeout -k 10 300 python bench.py --workload coupled1024ne$ne --steps 10 --warmup 3 --no-cpu-baseline --sustained-seconds 0 > $out/bench_ne${ne}_op$op.json 2> $out/bench_ne${ne}_op$op.err
+  QPSIM_COLL_ONEPASS=$op timeout -k 10 300 python bench.py --full --workload coupled1024ne$ne --steps 10 --warmup 3 --no-cpu-baseline --sustained-seconds 0 > $out/bench_ne${ne}_op$op.json 2> $out/bench_ne${ne}_op$op.err
   python - $out/bench_ne${ne}_op$op.json "ne$ne onepass=$op" <<'PY'
 import json,sys
 try:

@@ -2,7 +2,7 @@
 # (1) c3 / c4 with the phonon-prefetch depth of the single-pass collision kernel varied (tools/coll_pf_variants.sh);
 # (2) where the runtime copy / fill operations of the default-scheme bench sit in time (plan creation or steady state).
 out=gpurun_out/r3b; mkdir -p $out
-run() { tag=$1; wl=$2; shift 2; env "$@" timeout -k 10 300 python bench.py --workload $wl --steps 10 --warmup 3 --no-cpu-baseline --sustained-seconds 0 > $out/bench_${wl}_$tag.json 2> $out/bench_${wl}_$tag.err
+run() { tag=$1; wl=$2; shift 2; env "$@" timeout -k 10 300 python bench.py --full --workload $wl --steps 10 --warmup 3 --no-cpu-baseline --sustained-seconds 0 > $out/bench_${wl}_$tag.json 2> $out/bench_${wl}_$tag.err
   python - $out/bench_${wl}_$tag.json $wl-$tag <<'PY'
 import json,sys
 try:
@@ -16,7 +16,7 @@ for wl in c3 c4; do
   for n in 2 3 4; do [ -f tools/bin/libqpsim_pf$n.so ] && run pf$n $wl QPSIM_HIP_LIBRARY=$PWD/tools/bin/libqpsim_pf$n.so; done
 done
 R=$PWD; cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $R/$out/cntrace -o t -- python3 $R/bench.py --workload cn4096 --steps 20 --warmup 3 --no-cpu-baseline --sustained-seconds 0 > $R/$out/cntrace.json 2> $R/$out/cntrace.err
+rocprofv3 --kernel-trace --output-format csv -d $R/$out/cntrace -o t -- python3 $R/bench.py --full --workload cn4096 --steps 20 --warmup 3 --no-cpu-baseline --sustained-seconds 0 > $R/$out/cntrace.json 2> $R/$out/cntrace.err
 cd $R; python - $(find $out/cntrace -name "*kernel_trace.csv" | head -1) <<'PY'
 import csv,sys
 rows=list(csv.DictReader(open(sys.argv[1])))

@@ -8,6 +8,6 @@ mkdir -p $R/$out; cd /tmp; export TMPDIR=/tmp
 n=0
 for pass in "$@"; do
   n=$((n+1))
-  rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $R/$out/pass$n -o p -- python3 $R/bench.py $args --no-cpu-baseline > $R/$out/pass$n.log 2>&1
+  rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $R/$out/pass$n -o p -- python3 $R/bench.py --full $args --no-cpu-baseline > $R/$out/pass$n.log 2>&1
 done
 cd $R && python tools/pmc_counters.py $out $(find $out -name "*counter_collection.csv" | sort)

@@ -8,13 +8,13 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 mkdir -p $R/$out; cd /tmp; export TMPDIR=/tmp
 stats() {   # name, bench args
   want $1 || return 0
-  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/$1_stats -o s -- python3 $R/bench.py $2 --no-cpu-baseline --sustained-seconds 0 > $R/$out/$1_bench_under_rocprof.json 2> $R/$out/$1_stats.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/$1_stats -o s -- python3 $R/bench.py --full $2 --no-cpu-baseline --sustained-seconds 0 > $R/$out/$1_bench_under_rocprof.json 2> $R/$out/$1_stats.err
   cp $(find $R/$out/$1_stats -name "*kernel_stats.csv" | head -1) $R/$out/$1_kernel_stats.csv
 }
 traffic() { # name, bench args
   want $1 || return 0
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $R/$out/$1_fetch -o f -- python3 $R/bench.py $2 --no-cpu-baseline --sustained-seconds 0 > /dev/null 2> $R/$out/$1_fetch.err
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $R/$out/$1_write -o w -- python3 $R/bench.py $2 --no-cpu-baseline --sustained-seconds 0 > /dev/null 2> $R/$out/$1_write.err
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $R/$out/$1_fetch -o f -- python3 $R/bench.py --full $2 --no-cpu-baseline --sustained-seconds 0 > /dev/null 2> $R/$out/$1_fetch.err
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $R/$out/$1_write -o w -- python3 $R/bench.py --full $2 --no-cpu-baseline --sustained-seconds 0 > /dev/null 2> $R/$out/$1_write.err
   (cd $R && python tools/pmc_summary.py $(find $out/$1_fetch -name "*counter_collection.csv") $(find $out/$1_write -name "*counter_collection.csv") $out/$1_pmc.json > $out/$1_pmc.txt 2>&1)
 }
 stats adi4096 "--steps 50 --warmup 10"
