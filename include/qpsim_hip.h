@@ -248,6 +248,44 @@ int qp_pauli_stats(const double* state, const double* rho, const int32_t* cls, c
                    int32_t nclass, int64_t ncell, double density_floor, void* workspace, double* out_vals,
                    int64_t* out_idx, void* stream);
 
+/*
+ * Ensembles: `members` independent problems of ncell_member cells each, laid out [bin][member][cell] (state[ne][members *
+ * ncell_member]; flags and cls cover all members * ncell_member cells).
+ * qp_pauli_stats_members: for every member m, out_vals[m], out_idx[2m], out_idx[2m+1] are what qp_pauli_stats returns on
+ * member m's slice alone, bit for bit - indices member-local (ie * ncell_member + c), same tie and NaN rules.  Deterministic
+ * (per-block partials that never straddle two members, one finishing block per member; no atomics).
+ * workspace: qp_pauli_members_workspace_bytes(ncell_member, members) bytes.
+ */
+int64_t qp_pauli_members_workspace_bytes(int64_t ncell_member, int64_t members);
+int qp_pauli_stats_members(const double* state, const double* rho, const int32_t* cls, const uint8_t* flags, int32_t ne,
+                           int32_t nclass, int64_t ncell_member, int64_t members, double density_floor, void* workspace,
+                           double* out_vals, int64_t* out_idx, void* stream);
+/* state[f][m * ncell_member + c] += amounts[m] on interior cells (amounts: device array of `members` doubles); per member
+ * bit-equal to qp_add_constant on that member's slice (generation with per-member rates or pulse windows). */
+int qp_add_constant_members(const uint8_t* flags, int64_t ncell_member, int64_t members, int32_t nfield, double* state,
+                            const double* amounts, void* stream);
+/*
+ * qp_collision_step_guarded / qp_collision_double_step_guarded with the guard reduced PER MEMBER (out_vals[members],
+ * out_idx[2 * members] as qp_pauli_stats_members).  ncell = members * ncell_member.  When ncell_member % 64 == 0 every wave
+ * partial of the fused guard belongs to one member and a finishing kernel groups them (no extra pass over the state);
+ * otherwise, or when the kernel has no fused guard, the single-step call runs qp_pauli_stats_members on state_out.  The
+ * double-step call returns QP_ERR_UNSUPPORTED (nothing launched) in those cases, since its intermediate state never exists
+ * in memory, and wherever qp_collision_double_step_guarded would (incl. ncell >= 2^28).
+ * guard_workspace: max(qp_collision_guard_workspace_bytes(ncell), qp_pauli_members_workspace_bytes(ncell_member, members)).
+ */
+int qp_collision_step_guarded_members(const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
+                                      const double* state_in, double* state_out, double* phonon, double* ph_scratch,
+                                      double dE, double dt, int enable_recombination, int enable_scattering,
+                                      int update_phonons, double density_floor, void* guard_workspace,
+                                      int64_t ncell_member, int64_t members, double* out_vals, int64_t* out_idx,
+                                      void* stream);
+int qp_collision_double_step_guarded_members(const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
+                                             const double* state_in, double* state_out, double* phonon, double dE,
+                                             double dt_first, double dt_second, double gen_amount, int enable_recombination,
+                                             int enable_scattering, int update_phonons, double density_floor,
+                                             void* guard_workspace, int64_t ncell_member, int64_t members,
+                                             double* out_vals, int64_t* out_idx, void* stream);
+
 /* out[p] = dE * sum_i state[i][p]  (energy integral of solver.py:1367,1480; sequential in i). */
 int qp_energy_integrate(const double* state, int32_t ne, int64_t ncell, double dE, double* out, void* stream);
 

@@ -371,3 +371,76 @@ extern "C" int qp_collision_onepass_available(int32_t ne) { return qp::collision
 
 // 2nd bit: the gap-class variant (separable kernel tables, qp_collision_tables::gap_sq ...) exists as well
 extern "C" int qp_collision_register_kernel_classes(int32_t ne) { return qp::collision_fast_classes_supported(ne); }
+
+// ---------------------------------------------------------------------------------------------------------
+// Ensembles: the guarded calls with the Pauli guard reduced per member (qp_pauli_stats_members semantics).  The register
+// and pair kernels write one partial per wave of 64 consecutive pixels; with ncell_member % 64 == 0 no wave straddles two
+// members, so one finishing block per member groups them (64 w / ncell_member) without another pass over the state.
+// ---------------------------------------------------------------------------------------------------------
+static int members_args_ok(int64_t ncell, int64_t ncell_member, int64_t members, const char* who) {
+  if (ncell_member <= 0 || members <= 0 || ncell_member * members != ncell) {
+    qp::set_error("%s: ncell (%lld) must equal ncell_member (%lld) * members (%lld)", who, (long long)ncell,
+                  (long long)ncell_member, (long long)members);
+    return 0;
+  }
+  return 1;
+}
+
+extern "C" int qp_collision_step_guarded_members(const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
+                                                 const double* state_in, double* state_out, double* phonon,
+                                                 double* ph_scratch, double dE, double dt, int enable_recombination,
+                                                 int enable_scattering, int update_phonons, double density_floor,
+                                                 void* guard_workspace, int64_t ncell_member, int64_t members,
+                                                 double* out_vals, int64_t* out_idx, void* stream) {
+  QP_REQUIRE(guard_workspace && out_vals && out_idx, "guard_workspace, out_vals, out_idx must be non-NULL");
+  if (!members_args_ok(ncell, ncell_member, members, "qp_collision_step_guarded_members")) return QP_ERR_INVALID_ARGUMENT;
+  auto* parts = (qp::PauliPartial*)guard_workspace;
+  const bool aligned = ncell_member % 64 == 0;
+  bool done = false;
+  const int rc = collision_step_impl(t, flags, ncell, state_in, state_out, phonon, ph_scratch, dE, dt, enable_recombination,
+                                     enable_scattering, update_phonons, aligned ? parts + qp::kGuardMergeBlocks : nullptr,
+                                     density_floor, aligned ? &done : nullptr, stream);
+  if (rc != QP_OK) return rc;
+  if (done) {
+    qp::pauli_finish_members(parts + qp::kGuardMergeBlocks, (long)ncell_member, (long)members, out_vals, (long*)out_idx,
+                             (hipStream_t)stream);
+    return qp::check_launch("qp_collision_step_guarded_members");
+  }
+  return qp_pauli_stats_members(state_out, t->rho, t->cls, flags, t->ne, t->nclass, ncell_member, members, density_floor,
+                                guard_workspace, out_vals, out_idx, stream);
+}
+
+extern "C" int qp_collision_double_step_guarded_members(const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
+                                                        const double* state_in, double* state_out, double* phonon,
+                                                        double dE, double dt_first, double dt_second, double gen_amount,
+                                                        int enable_recombination, int enable_scattering, int update_phonons,
+                                                        double density_floor, void* guard_workspace, int64_t ncell_member,
+                                                        int64_t members, double* out_vals, int64_t* out_idx, void* stream) {
+  QP_REQUIRE(t != nullptr, "tables are NULL");
+  if (t->struct_size != sizeof(qp_collision_tables)) {
+    qp::set_error("qp_collision_double_step_guarded_members: qp_collision_tables.struct_size is %u, this library expects %zu",
+                  t->struct_size, sizeof(qp_collision_tables));
+    return QP_ERR_INVALID_ARGUMENT;
+  }
+  QP_REQUIRE(flags && state_in && state_out && phonon && state_in != state_out, "flags, state_in, state_out (distinct), phonon");
+  QP_REQUIRE(guard_workspace && out_vals && out_idx, "guard_workspace, out_vals, out_idx must be non-NULL");
+  QP_REQUIRE(ncell > 0 && t->rho != nullptr, "ncell must be positive, rho non-NULL");
+  if (!members_args_ok(ncell, ncell_member, members, "qp_collision_double_step_guarded_members")) return QP_ERR_INVALID_ARGUMENT;
+  if (ncell_member % 64 != 0) {
+    qp::set_error("qp_collision_double_step_guarded_members: ncell_member (%lld) is not a multiple of 64",
+                  (long long)ncell_member);
+    return QP_ERR_UNSUPPORTED;
+  }
+  const bool s = enable_scattering && t->ks0, r = enable_recombination && t->kr0;
+  auto* parts = (qp::PauliPartial*)guard_workspace;
+  if (!qp::collision_pair_dispatch(*t, flags, (long)ncell, state_in, state_out, phonon, dE, dt_first, dt_second, gen_amount, s, r,
+                                   update_phonons && (s || r), parts + qp::kGuardMergeBlocks, density_floor,
+                                   (hipStream_t)stream)) {
+    qp::set_error("qp_collision_double_step_guarded_members: no fused double half-step kernel for these tables "
+                  "(ne = %d, ncell = %lld)", t->ne, (long long)ncell);
+    return QP_ERR_UNSUPPORTED;
+  }
+  qp::pauli_finish_members(parts + qp::kGuardMergeBlocks, (long)ncell_member, (long)members, out_vals, (long*)out_idx,
+                           (hipStream_t)stream);
+  return qp::check_launch("qp_collision_double_step_guarded_members");
+}

@@ -64,6 +64,11 @@ constexpr int kGuardMergeBlocks = 512;
 void pauli_finish(const PauliPartial* parts, long nparts, PauliPartial* scratch, double* out_vals, long* out_idx,
                   hipStream_t stream);
 
+// per-member finish of the same wave partials (ensembles, ncell_member % 64 == 0): member m reduces the partials of waves
+// [m * ncell_member / 64, (m + 1) * ncell_member / 64) and reports member-local indices (qp_pauli_stats_members)
+void pauli_finish_members(const PauliPartial* parts, long ncell_member, long members, double* out_vals, long* out_idx,
+                          hipStream_t stream);
+
 // out[0] = max over `nparts` per-block maxima (second stage of qp_absmax, shared with qp_adi_rect_combine)
 void absmax_finish(const double* parts, int nparts, double* out, hipStream_t stream);
 

@@ -149,6 +149,88 @@ void pauli_finish(const PauliPartial* parts, long nparts, PauliPartial* scratch,
                      out_vals, out_idx);
 }
 
+// ---- per-member Pauli guard (ensembles: state[ne][members * ncm], member m owns cells [m * ncm, (m + 1) * ncm)) --------
+// Blocks never straddle two members: block x = m * bxm + b covers member m only.  Indices are formed member-local
+// (ie * ncm + c) from the start, so the merge order equals member m's own C order and pauli_better picks the winner of
+// qp_pauli_stats on that slice alone.
+__global__ void __launch_bounds__(256) pauli_members_partial_kernel(const double* __restrict__ s,
+                                                                    const double* __restrict__ rho,
+                                                                    const int32_t* __restrict__ cls,
+                                                                    const uint8_t* __restrict__ flags, int ne, long ncm,
+                                                                    long members, int bxm, double floor_,
+                                                                    PauliPartial* part) {
+  const long m = blockIdx.x / bxm;
+  const int b = blockIdx.x % bxm;
+  const long ncell = ncm * members;
+  double f = -__builtin_huge_val();
+  long fi = 0x7fffffffffffffffL, forb = -1;
+  const long stride = (long)bxm * blockDim.x;
+  for (int i = blockIdx.y; i < ne; i += gridDim.y) {
+    const double* si = s + (long)i * ncell + m * ncm;
+    const uint8_t* fm = flags + m * ncm;
+    const int32_t* cm = cls ? cls + m * ncm : nullptr;
+    const double r0 = rho[i];
+    for (long c = (long)b * blockDim.x + threadIdx.x; c < ncm; c += stride) {
+      if (!(fm[c] & QP_FLAG_ACTIVE)) continue;
+      const double r = cm ? rho[(long)cm[c] * ne + i] : r0;
+      const double n = si[c];
+      const long t = (long)i * ncm + c;
+      double occ = 0.0;
+      if (r > 1e-30) occ = n / fmax(r, 1e-30);
+      else if (n > floor_ && (forb < 0 || t < forb)) forb = t;
+      if (pauli_better(occ, t, f, fi)) { f = occ; fi = t; }
+    }
+  }
+  pauli_block_reduce(f, fi, forb, part + (m * gridDim.y + blockIdx.y) * bxm + b);
+}
+
+// block m merges member m's `per` contiguous partials; `wave_ncell` > 0: the partials are the per-wave ones of the fused
+// guard (global indices ie * ncell + p, converted here to member-local ie * ncm + c)
+__global__ void __launch_bounds__(256) pauli_members_final_kernel(const PauliPartial* part, long per, long ncm,
+                                                                  long wave_ncell, double* out_vals, long* out_idx) {
+  const long m = blockIdx.x;
+  double f = -__builtin_huge_val();
+  long fi = 0x7fffffffffffffffL, forb = -1;
+  for (long k = m * per + threadIdx.x; k < (m + 1) * per; k += blockDim.x)
+    pauli_merge(f, fi, forb, part[k].maxf, part[k].maxidx, part[k].forb);
+  __shared__ PauliPartial res;
+  pauli_block_reduce(f, fi, forb, &res);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    long mi = res.maxidx, fb = res.forb;
+    if (wave_ncell > 0) {      // global linear index -> member-local (the pixel lies in member m by construction)
+      if (mi >= 0 && mi != 0x7fffffffffffffffL) mi = (mi / wave_ncell) * ncm + (mi % wave_ncell - m * ncm);
+      if (fb >= 0) fb = (fb / wave_ncell) * ncm + (fb % wave_ncell - m * ncm);
+    }
+    out_vals[m] = res.maxf;
+    out_idx[2 * m] = mi;
+    out_idx[2 * m + 1] = fb;
+  }
+}
+
+void pauli_finish_members(const PauliPartial* parts, long ncell_member, long members, double* out_vals, long* out_idx,
+                          hipStream_t stream) {
+  hipLaunchKernelGGL(pauli_members_final_kernel, dim3((unsigned)members), dim3(256), 0, stream, parts, ncell_member / 64,
+                     ncell_member, ncell_member * members, out_vals, out_idx);
+}
+
+// blocks per member of the standalone pass: ~2048 blocks in all, at most kRedBlocks per member
+static inline long pauli_member_budget(long members) {
+  long b = 2048 / (members > 0 ? members : 1);
+  return b < 1 ? 1 : (b > kRedBlocks ? kRedBlocks : b);
+}
+
+__global__ void __launch_bounds__(256) add_constant_members_kernel(const uint8_t* __restrict__ flags, long ncm, long members,
+                                                                   int nfield, double* __restrict__ s,
+                                                                   const double* __restrict__ amounts) {
+  const long ncell = ncm * members;
+  const long total = ncell * nfield;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+    const long p = t % ncell;
+    if (flags[p] & QP_FLAG_ACTIVE) s[t] += amounts[p / ncm];
+  }
+}
+
 __global__ void __launch_bounds__(256) absmax_partial_kernel(const double* __restrict__ a, long n, double* part) {
   double m = 0.0;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) {
@@ -292,6 +374,41 @@ int qp_pauli_stats(const double* state, const double* rho, const int32_t* cls, c
   hipLaunchKernelGGL(qp::pauli_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, (int)blocks, out_vals,
                      (long*)out_idx);
   return qp::check_launch("qp_pauli_stats");
+}
+
+int64_t qp_pauli_members_workspace_bytes(int64_t ncell_member, int64_t members) {
+  (void)ncell_member;
+  if (members < 1) members = 1;
+  return (int64_t)members * qp::pauli_member_budget((long)members) * (int64_t)sizeof(qp::PauliPartial);
+}
+
+int qp_pauli_stats_members(const double* state, const double* rho, const int32_t* cls, const uint8_t* flags, int32_t ne,
+                           int32_t nclass, int64_t ncell_member, int64_t members, double density_floor, void* workspace,
+                           double* out_vals, int64_t* out_idx, void* stream) {
+  QP_REQUIRE(state && rho && flags && workspace && out_vals && out_idx, "NULL argument");
+  QP_REQUIRE(ne > 0 && nclass > 0 && ncell_member > 0 && members > 0, "ne, nclass, ncell_member, members must be positive");
+  QP_REQUIRE(members <= 0x7fffffffL / 1024, "too many members for one launch");
+  QP_REQUIRE(nclass == 1 || cls, "cls is required when nclass > 1");
+  const long budget = qp::pauli_member_budget((long)members);
+  const long by = ne < budget ? ne : budget;
+  long bxm = (ncell_member + 255) / 256;
+  if (bxm > budget / by) bxm = budget / by;
+  if (bxm < 1) bxm = 1;
+  auto* part = (qp::PauliPartial*)workspace;
+  hipLaunchKernelGGL(qp::pauli_members_partial_kernel, dim3((unsigned)(bxm * members), (unsigned)by), dim3(256), 0,
+                     (hipStream_t)stream, state, rho, cls, flags, (int)ne, (long)ncell_member, (long)members, (int)bxm,
+                     density_floor, part);
+  hipLaunchKernelGGL(qp::pauli_members_final_kernel, dim3((unsigned)members), dim3(256), 0, (hipStream_t)stream,
+                     (const qp::PauliPartial*)part, bxm * by, (long)ncell_member, 0L, out_vals, (long*)out_idx);
+  return qp::check_launch("qp_pauli_stats_members");
+}
+
+int qp_add_constant_members(const uint8_t* flags, int64_t ncell_member, int64_t members, int32_t nfield, double* state,
+                            const double* amounts, void* stream) {
+  QP_REQUIRE(flags && state && amounts && ncell_member > 0 && members > 0 && nfield > 0, "bad arguments");
+  hipLaunchKernelGGL(qp::add_constant_members_kernel, dim3(qp::grid_for(ncell_member * members * nfield)), dim3(256), 0,
+                     (hipStream_t)stream, flags, (long)ncell_member, (long)members, (int)nfield, state, amounts);
+  return qp::check_launch("qp_add_constant_members");
 }
 
 int qp_energy_integrate(const double* state, int32_t ne, int64_t ncell, double dE, double* out, void* stream) {

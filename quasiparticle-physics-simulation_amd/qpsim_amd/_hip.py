@@ -76,6 +76,17 @@ SIGNATURES = {
     "qp_pauli_stats": (C.c_int, [c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_int64, C.c_double, c_dp, c_dp,
                                  c_dp, c_dp]),
     "qp_energy_integrate": (C.c_int, [c_dp, C.c_int32, C.c_int64, C.c_double, c_dp, c_dp]),
+    "qp_pauli_members_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "qp_pauli_stats_members": (C.c_int, [c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double,
+                                         c_dp, c_dp, c_dp, c_dp]),
+    "qp_add_constant_members": (C.c_int, [c_dp, C.c_int64, C.c_int64, C.c_int32, c_dp, c_dp, c_dp]),
+    "qp_collision_step_guarded_members": (C.c_int, [C.POINTER(CollisionTables), c_dp, C.c_int64, c_dp, c_dp, c_dp, c_dp,
+                                                    C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double, c_dp,
+                                                    C.c_int64, C.c_int64, c_dp, c_dp, c_dp]),
+    "qp_collision_double_step_guarded_members": (C.c_int, [C.POINTER(CollisionTables), c_dp, C.c_int64, c_dp, c_dp, c_dp,
+                                                           C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                                                           C.c_int, C.c_double, c_dp, C.c_int64, C.c_int64, c_dp, c_dp,
+                                                           c_dp]),
     "qp_weighted_sum": (C.c_int, [c_dp, c_dp, C.c_int32, C.c_int64, c_dp, c_dp]),
     "qp_absmax": (C.c_int, [c_dp, C.c_int64, c_dp, c_dp, c_dp]),
     "qp_axpy": (C.c_int, [C.c_int64, C.c_double, c_dp, c_dp, c_dp]),

@@ -826,12 +826,13 @@ class Engine:
 
     # -- collisions, generation, reductions -------------------------------------------------------------------
     def make_collision_tables(self, kr0, ks0, rho, idx_diff, idx_sum, sign, cls_packed=None, allow_fast=True,
-                              kernel: str = "auto", gap_params: dict | None = None):
+                              kernel: str = "auto", gap_params: dict | None = None, members: int = 1):
         """Upload per-gap-class tables ([C,NE,NE], [C,NE]) and maps; returns an opaque handle.
 
         ``kernel``: "auto" | "generic" | "wave" | "wave_unstructured" forces a collision kernel (tests, A/B timing).
         ``gap_params`` (gap classes only): ``dict(E=E_bins, gaps=class_gaps, tau_r=, tau_s=, T_c=)`` - lets the register
-        kernel form K^r_0, K^s_0 per pixel from gap-independent tables (they are separable in the gap)."""
+        kernel form K^r_0, K^s_0 per pixel from gap-independent tables (they are separable in the gap).
+        ``members`` > 1: the class map is repeated over an ensemble laid out [member][cell] (same tables for every member)."""
         torch = self.torch
         up = lambda a, dt: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.device)  # noqa: E731
         rho = np.atleast_2d(np.asarray(rho, dtype=np.float64))
@@ -846,7 +847,7 @@ class Engine:
                 raise ValueError("cls is required for more than one gap class")
             full = np.zeros(self.ncell, dtype=np.int32)
             full[self.mask_flat] = np.asarray(cls_packed, dtype=np.int32)
-            h["cls"] = up(full, np.int32)
+            h["cls"] = up(np.tile(full, int(members)), np.int32)
         h["nw"] = nw
         h["diag_bin"] = h["anti_bin"] = None
         h["merged_slots"] = 0
@@ -913,12 +914,15 @@ class Engine:
                                            _ptr(h["ks0_diag"]), _ptr(h["kr0_anti2"]))
         return h
 
-    def collide(self, tables, state, state_out, phonon, dE, dt, en_r, en_s, update_phonons):
+    def collide(self, tables, state, state_out, phonon, dE, dt, en_r, en_s, update_phonons, ncell: int | None = None,
+                flags=None):
+        """One collision update; ``ncell`` / ``flags`` override the engine's grid (ensembles: members x cells)."""
+        nc = self.ncell if ncell is None else int(ncell)
         need_acc = update_phonons and (en_r or en_s) and not tables["fast"]
-        acc = self.scratch("coll_acc", 2 * tables["nw"] * self.ncell) if need_acc else None
+        acc = self.scratch("coll_acc", 2 * tables["nw"] * nc) if need_acc else None
         if tables["kernel"] == "register" and tables["merged_slots"] and update_phonons and en_r and en_s:
-            acc = self.scratch("coll_acc", 2 * tables["merged_slots"] * self.ncell)      # merged-bin stash
-        _hip.check(self.lib.qp_collision_step(C.byref(tables["struct"]), _ptr(self.d_flags), self.ncell, _ptr(state),
+            acc = self.scratch("coll_acc", 2 * tables["merged_slots"] * nc)      # merged-bin stash
+        _hip.check(self.lib.qp_collision_step(C.byref(tables["struct"]), _ptr(self.d_flags if flags is None else flags), nc, _ptr(state),
                                               _ptr(state_out), _ptr(phonon), _ptr(acc), float(dE), float(dt),
                                               int(bool(en_r)), int(bool(en_s)), int(bool(update_phonons)), self.stream),
                    "qp_collision_step")
@@ -1027,6 +1031,107 @@ class Engine:
         top = (i0 // nc, i0 % nc)
         forb = None if i1 < 0 else (i1 // nc, i1 % nc)
         return mx, top, forb
+
+    # -- ensembles: `members` problems of this geometry laid out [bin][member][cell]; the guard is reduced per member ----
+    def _members_guard_buffers(self, members: int):
+        """Device result buffer [vals | argmax, forbidden per member] (members x 24 bytes: one read-back copy per ticket) and
+        its ring of GUARD_LAG + 1 pinned host images, per ensemble size."""
+        torch = self.torch
+        cache = self.__dict__.setdefault("_mguard", {})
+        if members not in cache:
+            dev = torch.zeros(3 * members, dtype=torch.int64, device=self.device)
+            ring = [(torch.empty(3 * members, dtype=torch.int64).pin_memory(), torch.cuda.Event())
+                    for _ in range(self.GUARD_LAG + 1)]
+            cache[members] = {"dev": dev, "ring": ring, "next": 0}
+        return cache[members]
+
+    def _members_ws(self, ncell_member: int, members: int):
+        nbytes = max(int(self.lib.qp_collision_guard_workspace_bytes(ncell_member * members)),
+                     int(self.lib.qp_pauli_members_workspace_bytes(ncell_member, members)))
+        ws = getattr(self, "_mguard_ws", None)
+        if ws is None or ws.numel() < nbytes:
+            ws = self._mguard_ws = self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.device)
+        return ws
+
+    def _members_launch(self, tables, ncell_member: int, members: int, call):
+        """Runs ``call(ws, out_vals, out_idx)`` and enqueues the asynchronous read-back of its per-member results."""
+        b = self._members_guard_buffers(members)
+        host, ev = b["ring"][b["next"]]
+        b["next"] = (b["next"] + 1) % len(b["ring"])
+        dev = b["dev"]
+        call(self._members_ws(ncell_member, members), _ptr(dev[:members]), _ptr(dev[members:]))
+        host.copy_(dev, non_blocking=True)
+        ev.record(self.torch.cuda.current_stream(self.device))
+        return host, ev, int(ncell_member), int(members), int(tables["ne"])
+
+    def pauli_stats_members_launch(self, state, tables, floor: float, ncell_member: int, members: int, flags):
+        """Per-member Pauli guard (``qp_pauli_stats_members``) + read-back; ticket for ``pauli_stats_members_result``."""
+        def call(ws, vals, idx):
+            _hip.check(self.lib.qp_pauli_stats_members(_ptr(state), _ptr(tables["rho"]), _ptr(tables["cls"]), _ptr(flags),
+                                                       tables["ne"], tables["nclass"], int(ncell_member), int(members),
+                                                       float(floor), _ptr(ws), vals, idx, self.stream),
+                       "qp_pauli_stats_members")
+        return self._members_launch(tables, ncell_member, members, call)
+
+    def pauli_stats_members_result(self, ticket):
+        """[(max occupation, (energy index, member cell index), forbidden (energy, cell) or None)] per member, each as
+        ``pauli_stats_result`` of that member's lone run."""
+        host, ev, ncm, members, ne = ticket
+        ev.synchronize()
+        vals = host[:members].view(self.torch.float64).numpy().copy()
+        idx = host[members:].numpy().copy()
+        out = []
+        for m in range(members):
+            i0, i1 = int(idx[2 * m]), int(idx[2 * m + 1])
+            i0 = min(max(i0, 0), ncm * ne - 1)
+            out.append((float(vals[m]), (i0 // ncm, i0 % ncm), None if i1 < 0 else (i1 // ncm, i1 % ncm)))
+        return out
+
+    def collide_guarded_members(self, tables, state, state_out, phonon, dE, dt, en_r, en_s, update_phonons, floor: float,
+                                ncell_member: int, members: int, flags):
+        """``collide_guarded`` over an ensemble with the guard reduced per member (``qp_collision_step_guarded_members``)."""
+        nc = int(ncell_member) * int(members)
+        need_acc = update_phonons and (en_r or en_s) and not tables["fast"]
+        acc = self.scratch("coll_acc", 2 * tables["nw"] * nc) if need_acc else None
+        if tables["kernel"] == "register" and tables["merged_slots"] and update_phonons and en_r and en_s:
+            acc = self.scratch("coll_acc", 2 * tables["merged_slots"] * nc)
+
+        def call(ws, vals, idx):
+            _hip.check(self.lib.qp_collision_step_guarded_members(
+                C.byref(tables["struct"]), _ptr(flags), nc, _ptr(state), _ptr(state_out), _ptr(phonon), _ptr(acc),
+                float(dE), float(dt), int(bool(en_r)), int(bool(en_s)), int(bool(update_phonons)), float(floor), _ptr(ws),
+                int(ncell_member), int(members), vals, idx, self.stream), "qp_collision_step_guarded_members")
+        return self._members_launch(tables, ncell_member, members, call)
+
+    @staticmethod
+    def pair_members_supported(tables, ncell_member: int, members: int) -> bool:
+        """Whether ``qp_collision_double_step_guarded_members`` accepts this ensemble (else two calls per step pair)."""
+        return bool(tables.get("pair")) and ncell_member % 64 == 0 and ncell_member * members < (1 << 28)
+
+    def collide_pair_guarded_members(self, tables, state, state_out, phonon, dE, dt_first, dt_second, gen_amount, en_r,
+                                     en_s, update_phonons, floor: float, ncell_member: int, members: int, flags):
+        """``collide_pair_guarded`` over an ensemble, guard per member (only when ``pair_members_supported``)."""
+        nc = int(ncell_member) * int(members)
+
+        def call(ws, vals, idx):
+            _hip.check(self.lib.qp_collision_double_step_guarded_members(
+                C.byref(tables["struct"]), _ptr(flags), nc, _ptr(state), _ptr(state_out), _ptr(phonon), float(dE),
+                float(dt_first), float(dt_second), float(gen_amount), int(bool(en_r)), int(bool(en_s)),
+                int(bool(update_phonons)), float(floor), _ptr(ws), int(ncell_member), int(members), vals, idx, self.stream),
+                "qp_collision_double_step_guarded_members")
+        return self._members_launch(tables, ncell_member, members, call)
+
+    def add_constant_members(self, state, amounts: tuple, ncell_member: int, members: int, flags):
+        """state[f][m * ncell_member + c] += amounts[m] on interior cells.  The device vectors are cached by value: constant
+        and pulse generation take few distinct per-member patterns, so no step uploads synchronously."""
+        cache = self.__dict__.setdefault("_amount_vectors", {})
+        key = tuple(float(a) for a in amounts)
+        vec = cache.get(key)
+        if vec is None:
+            vec = cache[key] = self.torch.as_tensor(np.asarray(key, dtype=np.float64), device=self.device)
+        nfield = state.numel() // (int(ncell_member) * int(members))
+        _hip.check(self.lib.qp_add_constant_members(_ptr(flags), int(ncell_member), int(members), int(nfield), _ptr(state),
+                                                    _ptr(vec), self.stream), "qp_add_constant_members")
 
     def energy_integral(self, state, dE: float):
         out = self.empty(self.ncell)

@@ -288,6 +288,159 @@ class _Diffuser:
             self.step(u, True)
 
 
+def _checked_run_arguments(mask, initial_field, diffusion_coefficient, dt, total_time, store_every, enable_diffusion,
+                           enable_recombination, enable_scattering, tau_0, tau_s, tau_r, external_generation,
+                           phonon_history_out):
+    """Argument checks of a run, in the reference's order and with its messages (solver.py:1040-1080); clears
+    ``phonon_history_out``.  Returns (mask, initial_field, store_every, n interior cells, tau_s, tau_r)."""
+    mask = np.asarray(mask, dtype=bool)
+    initial_field = np.asarray(initial_field)
+    if dt <= 0 or total_time <= 0:
+        raise ValueError("dt and total_time must be positive.")
+    if enable_diffusion and diffusion_coefficient <= 0:
+        raise ValueError("Diffusion coefficient must be positive.")
+    if store_every <= 0:
+        store_every = 1
+    if initial_field.shape != mask.shape:
+        raise ValueError("Initial field shape must match mask shape.")
+    n = int(np.sum(mask))
+    if n == 0:
+        raise ValueError("Geometry mask has no interior points.")
+    if phonon_history_out is not None:
+        phonon_history_out.clear()
+    tau_s_eff = float(tau_s if tau_s is not None else tau_0)
+    tau_r_eff = float(tau_r if tau_r is not None else tau_0)
+    if enable_scattering and tau_s_eff <= 0:
+        raise ValueError("tau_s must be positive when scattering is enabled.")
+    if enable_recombination and tau_r_eff <= 0:
+        raise ValueError("tau_r must be positive when recombination is enabled.")
+    if external_generation is not None:
+        external_generation.validate()
+    return mask, initial_field, store_every, n, tau_s_eff, tau_r_eff
+
+
+def _run_geometry(mask, edges, edge_conditions, dx, enable_diffusion):
+    """Compiled geometry of the device grid = bounding box of the mask."""
+    dev_mask, dev_edges = _crop_to_bounding_box(mask, edges)
+    if enable_diffusion:
+        return compile_geometry(dev_mask, dev_edges, edge_conditions, dx)
+    # no operator needed: boundary conditions are not consulted (solver.py:1081-1083)
+    from .engine import CompiledGeometry, link_flags
+    z = np.zeros(dev_mask.shape)
+    return CompiledGeometry(dev_mask, float(dx), link_flags(dev_mask), z, z, z, z)
+
+
+def _initial_qp_state(mask, initial_field, E_bins, dE, gap, dynes_gamma, energy_weights, initial_condition_spec):
+    """[NE, n] initial quasiparticle densities (solver.py:1240-1283)."""
+    NE, n = len(E_bins), int(np.sum(mask))
+    custom_state = None
+    if initial_condition_spec is not None:
+        from .initial_conditions import build_initial_qp_energy_state
+        custom_state = build_initial_qp_energy_state(mask=mask, E_bins=E_bins, spec=initial_condition_spec)
+    if custom_state is not None:
+        state_host = np.asarray(custom_state, dtype=float)
+        if state_host.shape != (NE, n):
+            raise ValueError(f"Full custom quasiparticle profile must have shape ({NE}, {n}); got {state_host.shape}.")
+        if not np.all(np.isfinite(state_host)):
+            raise ValueError("Full custom quasiparticle profile produced non-finite values.")
+        if np.any(state_host < 0):
+            raise ValueError("Full custom quasiparticle profile must be non-negative.")
+        return state_host
+    spatial = initial_field[mask].astype(float)
+    if energy_weights is not None:
+        raw = np.asarray(energy_weights, dtype=float)
+        if raw.ndim != 1:
+            raise ValueError("energy_weights must be a 1D array.")
+        if raw.shape[0] != NE:
+            raise ValueError(f"energy_weights must have length {NE}, got {raw.shape[0]}.")
+        if not np.all(np.isfinite(raw)):
+            raise ValueError("energy_weights must contain only finite values.")
+        if np.any(raw < 0):
+            raise ValueError("energy_weights must be non-negative.")
+    else:
+        raw = _dynes_density_of_states(E_bins, gap, dynes_gamma)
+    integral = np.sum(raw) * dE
+    weights = raw / integral if integral > 0 else np.ones(NE, dtype=float) / (NE * dE)
+    state_host = np.empty((NE, n), dtype=float)
+    for i in range(NE):
+        state_host[i] = spatial * weights[i]
+    return state_host
+
+
+def _initial_phonon_state(mask, omega_bins, bath_temperature, initial_condition_spec):
+    """[Nw, n] initial phonon occupations: thermal at the bath temperature or from the initial-condition spec."""
+    n = int(np.sum(mask))
+    if initial_condition_spec is not None:
+        from .initial_conditions import build_initial_phonon_energy_state
+        return build_initial_phonon_energy_state(mask=mask, omega_bins=omega_bins, spec=initial_condition_spec,
+                                                 bath_temperature=bath_temperature)
+    return thermal_phonon_occupation(omega_bins, bath_temperature)[:, None] * np.ones((1, n), dtype=float)
+
+
+def _collision_tables(eng, E_bins, gap, nonuniform_pre, n, dynes_gamma, tau_r_eff, tau_s_eff, T_c, enable_recombination,
+                      enable_scattering, idx_diff, idx_sum, diff_sign, members: int = 1):
+    """(device collision tables, rho per gap class) (solver.py:1189-1238); ``nonuniform_pre``: the precomputed arrays of a
+    non-uniform gap (one class per distinct gap value), None for one gap."""
+    if nonuniform_pre is not None:
+        gap_values = nonuniform_pre.get("gap_values")
+        gap_values = np.full(n, gap, dtype=float) if gap_values is None else np.asarray(gap_values, dtype=float)
+        class_gaps, cls = np.unique(gap_values, return_inverse=True)
+    else:
+        class_gaps, cls = np.array([gap], dtype=float), None
+    rho_tab = np.stack([_dynes_density_of_states(E_bins, float(g), dynes_gamma) for g in class_gaps])
+    kr_tab = (np.stack([recombination_kernel_base(E_bins, float(g), tau_r_eff, T_c) for g in class_gaps])
+              if enable_recombination else None)
+    ks_tab = (np.stack([scattering_kernel_base(E_bins, float(g), tau_s_eff, T_c) for g in class_gaps])
+              if enable_scattering else None)
+    ctab = eng.make_collision_tables(kr_tab, ks_tab, rho_tab, idx_diff, idx_sum, diff_sign, cls,
+                                     gap_params=dict(E=E_bins, gaps=class_gaps, tau_r=tau_r_eff, tau_s=tau_s_eff, T_c=T_c),
+                                     members=members)
+    return ctab, rho_tab
+
+
+def _generation_amount(spec, t_start: float, dt_of_step: float):
+    """dt g_ext of a step that starts at ``t_start`` when it is one number for all bins and pixels (constant / pulse
+    modes), None when it is not (custom mode); 0.0 without generation (the reference gates on the raw mode string,
+    solver.py:1459)."""
+    if spec is None or spec.mode == "none":
+        return 0.0
+    mode = spec.mode.strip().lower()
+    if mode == "constant":
+        return dt_of_step * float(spec.rate)
+    if mode == "pulse":
+        on = spec.pulse_start <= t_start < spec.pulse_start + spec.pulse_duration
+        return dt_of_step * float(spec.pulse_rate) if on else 0.0
+    return None if mode == "custom" else 0.0
+
+
+def _pauli_verdict(stats, step_idx: int, time_ns: float, E_bins, coords, cell_to_px, warned: bool, enforce_pauli: bool,
+                   warn_threshold, error_threshold):
+    """What the Pauli guard of one step does (solver.py:1296-1344): (error message or None, warning message or None,
+    warned).  At most one of the two messages is set."""
+    max_occ, (ie_max, cell_max), forb = stats
+    if forb is not None:
+        r, c = coords[cell_to_px[forb[1]]]
+        msg = (f"Detected non-zero quasiparticle density in forbidden state (rho≈0): step={step_idx}, "
+               f"t={time_ns:.6g} ns, E={E_bins[forb[0]]:.6g} μeV, pixel=({int(r)},{int(c)}).")
+        if enforce_pauli:
+            return msg, None, warned
+        if not warned:
+            return None, msg, True
+    r, c = coords[cell_to_px[cell_max]]
+    if error_threshold is not None and max_occ > error_threshold:
+        msg = (f"Pauli occupation exceeded limit: f={max_occ:.6g} > {error_threshold:.6g} "
+               f"at step={step_idx}, t={time_ns:.6g} ns, E={E_bins[ie_max]:.6g} μeV, pixel=({int(r)},{int(c)}).")
+        if enforce_pauli:
+            return msg, None, warned
+        if not warned:
+            return None, msg, True
+    if warn_threshold is not None and max_occ > warn_threshold and not warned:
+        return None, ("High occupation detected (Pauli blocking regime): "
+                      f"max f={max_occ:.6g} at step={step_idx}, t={time_ns:.6g} ns, "
+                      f"E={E_bins[ie_max]:.6g} μeV, pixel=({int(r)},{int(c)})."), True
+    return None, None, warned
+
+
 def _on_run_device(fn):
     """Runs ``fn`` with the HIP device of its ``device=`` argument current in the calling thread (kernel launches through
     the C ABI go to the thread's current device; the reference's GUI calls the solver from a worker thread)."""
@@ -356,41 +509,15 @@ def run_2d_crank_nicolson(
     Returns ``(times, frames, mass, color_limits, energy_frames_or_None, energy_bins_or_None)`` exactly
     as the reference does; ``phonon_history_out`` is cleared and filled the same way.
     """
-    mask = np.asarray(mask, dtype=bool)
-    initial_field = np.asarray(initial_field)
-    if dt <= 0 or total_time <= 0:
-        raise ValueError("dt and total_time must be positive.")
-    if enable_diffusion and diffusion_coefficient <= 0:
-        raise ValueError("Diffusion coefficient must be positive.")
-    if store_every <= 0:
-        store_every = 1
-    if initial_field.shape != mask.shape:
-        raise ValueError("Initial field shape must match mask shape.")
-    n = int(np.sum(mask))
-    if n == 0:
-        raise ValueError("Geometry mask has no interior points.")
-    if phonon_history_out is not None:
-        phonon_history_out.clear()
-    tau_s_eff = float(tau_s if tau_s is not None else tau_0)
-    tau_r_eff = float(tau_r if tau_r is not None else tau_0)
-    if enable_scattering and tau_s_eff <= 0:
-        raise ValueError("tau_s must be positive when scattering is enabled.")
-    if enable_recombination and tau_r_eff <= 0:
-        raise ValueError("tau_r must be positive when recombination is enabled.")
-    if external_generation is not None:
-        external_generation.validate()
+    mask, initial_field, store_every, n, tau_s_eff, tau_r_eff = _checked_run_arguments(
+        mask, initial_field, diffusion_coefficient, dt, total_time, store_every, enable_diffusion, enable_recombination,
+        enable_scattering, tau_0, tau_s, tau_r, external_generation, phonon_history_out)
 
     # Device grid = bounding box of the mask.  Interior cells keep their argwhere (row-major) order under the crop, so
     # the packed [NE, n] layout of every host-side array is unchanged; frames are still rebuilt on the full mask.  A
     # mask whose interior is a solid rectangle inside a padded frame (the reference's built-in geometry) thereby
     # becomes a full rectangle on the device and takes the tiled ADI path.
-    dev_mask, dev_edges = _crop_to_bounding_box(mask, edges)
-    if enable_diffusion:
-        geom = compile_geometry(dev_mask, dev_edges, edge_conditions, dx)
-    else:  # no operator needed: boundary conditions are not consulted (solver.py:1081-1083)
-        from .engine import CompiledGeometry, link_flags
-        z = np.zeros(dev_mask.shape)
-        geom = CompiledGeometry(dev_mask, float(dx), link_flags(dev_mask), z, z, z, z)
+    geom = _run_geometry(mask, edges, edge_conditions, dx, enable_diffusion)
     full_steps, rem, total_steps = _step_plan(total_time, dt)
     eng = Engine(geom, device=device)
     eng.pin_stream()          # one stream for the whole run: skip the per-launch lookup
@@ -405,10 +532,6 @@ def run_2d_crank_nicolson(
     gap = energy_gap
     NE = num_energy_bins
     E_bins, dE = build_energy_grid(gap, energy_min_factor, energy_max_factor, NE)
-    custom_state = None
-    if initial_condition_spec is not None:
-        from .initial_conditions import build_initial_qp_energy_state
-        custom_state = build_initial_qp_energy_state(mask=mask, E_bins=E_bins, spec=initial_condition_spec)
     if precomputed is None and gap_expression.strip():          # auto-precompute (solver.py:1106-1124)
         from .precompute import precompute_arrays
         params = SimulationParameters(
@@ -438,54 +561,12 @@ def run_2d_crank_nicolson(
 
     # collision tables (solver.py:1189-1238): phonon grid, thermal phonons, per-gap-class kernels
     omega_bins, idx_diff, idx_sum, diff_sign = _build_phonon_frequency_map(E_bins)
-    phonon_host = thermal_phonon_occupation(omega_bins, bath_temperature)[:, None] * np.ones((1, n), dtype=float)
-    if initial_condition_spec is not None:
-        from .initial_conditions import build_initial_phonon_energy_state
-        phonon_host = build_initial_phonon_energy_state(mask=mask, omega_bins=omega_bins, spec=initial_condition_spec,
-                                                        bath_temperature=bath_temperature)
-    if nonuniform:
-        gap_values = precomputed.get("gap_values")
-        gap_values = np.full(n, gap, dtype=float) if gap_values is None else np.asarray(gap_values, dtype=float)
-        class_gaps, cls = np.unique(gap_values, return_inverse=True)
-    else:
-        class_gaps, cls = np.array([gap], dtype=float), None
-    rho_tab = np.stack([_dynes_density_of_states(E_bins, float(g), dynes_gamma) for g in class_gaps])
-    kr_tab = (np.stack([recombination_kernel_base(E_bins, float(g), tau_r_eff, T_c) for g in class_gaps])
-              if enable_recombination else None)
-    ks_tab = (np.stack([scattering_kernel_base(E_bins, float(g), tau_s_eff, T_c) for g in class_gaps])
-              if enable_scattering else None)
-    ctab = eng.make_collision_tables(kr_tab, ks_tab, rho_tab, idx_diff, idx_sum, diff_sign, cls,
-                                     gap_params=dict(E=E_bins, gaps=class_gaps, tau_r=tau_r_eff, tau_s=tau_s_eff, T_c=T_c))
+    phonon_host = _initial_phonon_state(mask, omega_bins, bath_temperature, initial_condition_spec)
+    ctab, rho_tab = _collision_tables(eng, E_bins, gap, precomputed if nonuniform else None, n, dynes_gamma, tau_r_eff,
+                                      tau_s_eff, T_c, enable_recombination, enable_scattering, idx_diff, idx_sum, diff_sign)
 
-    # initial quasiparticle state (solver.py:1240-1283)
-    if custom_state is not None:
-        state_host = np.asarray(custom_state, dtype=float)
-        if state_host.shape != (NE, n):
-            raise ValueError(f"Full custom quasiparticle profile must have shape ({NE}, {n}); got {state_host.shape}.")
-        if not np.all(np.isfinite(state_host)):
-            raise ValueError("Full custom quasiparticle profile produced non-finite values.")
-        if np.any(state_host < 0):
-            raise ValueError("Full custom quasiparticle profile must be non-negative.")
-    else:
-        spatial = initial_field[mask].astype(float)
-        if energy_weights is not None:
-            raw = np.asarray(energy_weights, dtype=float)
-            if raw.ndim != 1:
-                raise ValueError("energy_weights must be a 1D array.")
-            if raw.shape[0] != NE:
-                raise ValueError(f"energy_weights must have length {NE}, got {raw.shape[0]}.")
-            if not np.all(np.isfinite(raw)):
-                raise ValueError("energy_weights must contain only finite values.")
-            if np.any(raw < 0):
-                raise ValueError("energy_weights must be non-negative.")
-        else:
-            raw = _dynes_density_of_states(E_bins, gap, dynes_gamma)
-        integral = np.sum(raw) * dE
-        weights = raw / integral if integral > 0 else np.ones(NE, dtype=float) / (NE * dE)
-        state_host = np.empty((NE, n), dtype=float)
-        for i in range(NE):
-            state_host[i] = spatial * weights[i]
-
+    state_host = _initial_qp_state(mask, initial_field, E_bins, dE, gap, dynes_gamma, energy_weights,
+                                   initial_condition_spec)
     state = eng.upload_packed(state_host)
     state_alt = eng.empty(NE, eng.ncell)
     phonon = eng.upload_packed(phonon_host)
@@ -510,30 +591,12 @@ def run_2d_crank_nicolson(
         nonlocal warned
         if stats is None:
             stats = eng.pauli_stats(state, ctab, pauli_density_floor)
-        max_occ, (ie_max, cell_max), forb = stats
-        if forb is not None:
-            r, c = coords[cell_to_px[forb[1]]]
-            msg = (f"Detected non-zero quasiparticle density in forbidden state (rho≈0): step={step_idx}, "
-                   f"t={time_ns:.6g} ns, E={E_bins[forb[0]]:.6g} μeV, pixel=({int(r)},{int(c)}).")
-            if enforce_pauli:
-                raise ValueError(msg)
-            if not warned:
-                warnings.warn(msg, stacklevel=3)
-                warned = True
-        r, c = coords[cell_to_px[cell_max]]
-        if pauli_error_threshold is not None and max_occ > pauli_error_threshold:
-            msg = (f"Pauli occupation exceeded limit: f={max_occ:.6g} > {pauli_error_threshold:.6g} "
-                   f"at step={step_idx}, t={time_ns:.6g} ns, E={E_bins[ie_max]:.6g} μeV, pixel=({int(r)},{int(c)}).")
-            if enforce_pauli:
-                raise ValueError(msg)
-            if not warned:
-                warnings.warn(msg, stacklevel=3)
-                warned = True
-        if pauli_warn_threshold is not None and max_occ > pauli_warn_threshold and not warned:
-            warnings.warn("High occupation detected (Pauli blocking regime): "
-                          f"max f={max_occ:.6g} at step={step_idx}, t={time_ns:.6g} ns, "
-                          f"E={E_bins[ie_max]:.6g} μeV, pixel=({int(r)},{int(c)}).", stacklevel=3)
-            warned = True
+        error, warning, warned = _pauli_verdict(stats, step_idx, time_ns, E_bins, coords, cell_to_px, warned, enforce_pauli,
+                                                pauli_warn_threshold, pauli_error_threshold)
+        if error is not None:
+            raise ValueError(error)
+        if warning is not None:
+            warnings.warn(warning, stacklevel=3)
 
     guard(0, 0.0)
 
@@ -609,17 +672,7 @@ def run_2d_crank_nicolson(
                        and pauli_error_threshold is None and pauli_warn_threshold is None
                        and float(np.min(rho_tab)) > 1e-30)
     def generation_amount(t_start: float, dt_of_step: float):
-        """dt g_ext of a step that starts at ``t_start`` when it is one number for all bins and pixels (constant / pulse
-        modes), None when it is not (custom mode); 0.0 without generation."""
-        if not gen_active:
-            return 0.0
-        if gen_mode == "constant":
-            return dt_of_step * float(external_generation.rate)
-        if gen_mode == "pulse":
-            on = external_generation.pulse_start <= t_start < (external_generation.pulse_start
-                                                               + external_generation.pulse_duration)
-            return dt_of_step * float(external_generation.pulse_rate) if on else 0.0
-        return None if gen_mode == "custom" else 0.0
+        return _generation_amount(external_generation, t_start, dt_of_step)
 
     current_time = 0.0
     done = 0
