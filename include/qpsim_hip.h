@@ -317,7 +317,9 @@ int qp_cheb_update(int64_t n, double c1, const double* z, double c2, double* d, 
  *              qp_adi_rect_plan_decoupled(plan, dir) reports which one a direction uses (1 / 0).
  * The plan owns its device tables and work planes (hipMalloc at creation, the only allocating call).
  * qp_adi_rect_steps advances u [nfield][ny*nx] in place by `nsteps` consecutive diffusion steps; intermediate
- * fields are not materialised (steady-state traffic: one read + one write of the field per sweep).
+ * fields are not materialised.  Steady-state traffic: one read + one write of the field per sweep (32 B per cell-update);
+ * on fine-tile plans of >= 4 Mi cells a read-only reduce pass + one fused pass per step (24 B per cell-update, same
+ * results bit for bit; QPSIM_ADI_FUSED=0 / 1 at plan creation forces the choice).
  */
 typedef struct qp_adi_rect_plan qp_adi_rect_plan;
 int qp_adi_rect_plan_create(int32_t ny, int32_t nx, int32_t nfield, double r, const double* dcoef_host,

@@ -219,30 +219,41 @@ __device__ __forceinline__ FineBlock fine_block(const FineView& v) {
   return f;
 }
 
-// x-kernel: finish the x-solve, apply the explicit x-operator, eliminate along y.   buf: rhs1 -> rhs2 in place
-template <bool EXPLICIT, int STREAM, bool SRC = false>
-__global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_x_kernel(FineView v, double* __restrict__ buf) {
-  __shared__ double lds[FINE_LDS_DOUBLES];
+// x-kernel tile: x-chunk tx x rows [64 ty, 64 ty + 64) of field b (fine_block).  Wave-uniform tile origin + a 32-bit lane
+// offset (half-wave h starts 32 rows further down).
+struct FineXTile {
+  int b, tx, ty;
+  long origin;       // element offset of the tile's first cell in a [nfield][ny*nx] plane
+  unsigned off;
+};
+__device__ __forceinline__ FineXTile fine_x_tile(const FineView& v) {
   const int lane = threadIdx.x, h = lane >> 5, c = lane & 31;
   const FineBlock fb = fine_block(v);
-  const int tx = 2 * fb.stx + fb.sub;  // x-chunk (32 columns)
-  const int ty = fb.sty;               // pair of y-chunks (64 rows)
-  const int b = fb.b;
+  FineXTile t;
+  t.tx = 2 * fb.stx + fb.sub;          // x-chunk (32 columns)
+  t.ty = fb.sty;                       // pair of y-chunks (64 rows)
+  t.b = fb.b;
+  t.origin = (long)t.b * ((long)v.ny * v.nx) + (long)(t.ty * 64) * v.nx + t.tx * FS;
+  t.off = (unsigned)(h * FS) * (unsigned)v.nx + (unsigned)c;
+  return t;
+}
+
+// Front half of every x-kernel tile: x-solve from rhs1 at `tile`, explicit x-operator (EXPLICIT), source plane (SRC), and
+// the transpose back - on return lane (h, c) holds y-chunk 2 ty + h of column 32 tx + c, register r = row 64 ty + 32 h + r.
+// parts[0] is the x-solve table; every part is warmed in the scalar cache while the rows are in flight.
+template <bool EXPLICIT, int STREAM, bool SRC, int NPART>
+__device__ __forceinline__ void fine_x_front(const FineView& v, const FineXTile& t, const double* tile,
+                                             const CoefFine (&parts)[NPART], double* lds, double (&e)[FS]) {
+  const int lane = threadIdx.x;
+  const int tx = t.tx, ty = t.ty, b = t.b;
+  const unsigned off = t.off;
   const long ncell = (long)v.ny * v.nx;
   const double a = as_const(v.alpha)[b];
   const int row = ty * 64 + lane;      // lane = row between the transposes
   const FineGhost graw = fine_ghost_prefetch(v, 0, b, tx, row);
-  const CoefFine cx = fine_coefs(v, 0, b, chunk_variant(tx, v.px), 0);
-  // wave-uniform tile origin + a 32-bit lane offset (half-wave h starts 32 rows further down)
-  double* tile = buf + (long)b * ncell + (long)(ty * 64) * v.nx + tx * FS;
-  unsigned off = (unsigned)(h * FS) * (unsigned)v.nx + (unsigned)c;
-  double e[FS];
+  const CoefFine cx = parts[0];
   fine_load_rows<STREAM>(tile + off, v.nx, e);
-  {
-    const CoefFine parts[3] = {cx, fine_coefs(v, 1, b, chunk_variant(2 * ty, v.py), 1),
-                               fine_coefs(v, 1, b, chunk_variant(2 * ty + 1, v.py), 1)};
-    warm_scalar_cache(parts);
-  }
+  warm_scalar_cache(parts);
   transpose32h(e, lds, lane);
   double gl, gr;
   fine_ghost_finish(v, 0, b, tx, graw, gl, gr);
@@ -264,15 +275,89 @@ __global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_x_kernel(FineView v, do
 #pragma unroll
     for (int r = 0; r < FS; ++r) e[r] = fma(v.bscale, bv[SRC ? r : 0], e[r]);
   }
-  asm volatile("" : "+v"(off));        // the 32 row addresses are formed again here instead of living through the solve
-  fine_store_rows<STREAM>(tile + off, v.nx, e);
-  if (QP_ABL & 8) return;
+}
+
+// y-elimination of the two y-chunks the x-kernel tile holds after fine_x_front -> iface[1]
+__device__ __forceinline__ void fine_x_ends(const FineView& v, const FineXTile& t, const double (&e)[FS]) {
+  const int lane = threadIdx.x, h = lane >> 5, c = lane & 31;
   double yf, yl;
-  ends32_pair(e, v, 1, b, 2 * ty, v.py, h, yf, yl);
-  double* ir = v.iface[1] + (long)b * (2 * v.py + 2) * v.nx + tx * FS + c;
-  const int yc = 2 * ty + h;
+  ends32_pair(e, v, 1, t.b, 2 * t.ty, v.py, h, yf, yl);
+  double* ir = v.iface[1] + (long)t.b * (2 * v.py + 2) * v.nx + t.tx * FS + c;
+  const int yc = 2 * t.ty + h;
   ir[(long)(2 * yc + 1) * v.nx] = yf;
   ir[(long)(2 * yc + 2) * v.nx] = yl;
+}
+
+__device__ __forceinline__ void fine_x_warm_parts(const FineView& v, const FineXTile& t, CoefFine (&parts)[3]) {
+  parts[0] = fine_coefs(v, 0, t.b, chunk_variant(t.tx, v.px), 0);
+  parts[1] = fine_coefs(v, 1, t.b, chunk_variant(2 * t.ty, v.py), 1);
+  parts[2] = fine_coefs(v, 1, t.b, chunk_variant(2 * t.ty + 1, v.py), 1);
+}
+
+// x-kernel: finish the x-solve, apply the explicit x-operator, eliminate along y.   buf: rhs1 -> rhs2 in place
+template <bool EXPLICIT, int STREAM, bool SRC = false>
+__global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_x_kernel(FineView v, double* __restrict__ buf) {
+  __shared__ double lds[FINE_LDS_DOUBLES];
+  FineXTile t = fine_x_tile(v);
+  double* tile = buf + t.origin;
+  CoefFine parts[3];
+  fine_x_warm_parts(v, t, parts);
+  double e[FS];
+  fine_x_front<EXPLICIT, STREAM, SRC>(v, t, tile, parts, lds, e);
+  asm volatile("" : "+v"(t.off));      // the 32 row addresses are formed again here instead of living through the solve
+  fine_store_rows<STREAM>(tile + t.off, v.nx, e);
+  if (QP_ABL & 8) return;
+  fine_x_ends(v, t, e);
+}
+
+// Reduce pass R of a fused ADI step (qp_adi_rect_steps): the x-kernel without its plane store - rhs1 is only read, and
+// what leaves the tile is the y-elimination of the rhs2 it holds (iface[1]).  fine_fused_kernel then forms the same rhs2
+// again (same code, same bits) and finishes the step with it.
+template <int STREAM>
+__global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_reduce_kernel(FineView v, const double* __restrict__ buf) {
+  __shared__ double lds[FINE_LDS_DOUBLES];
+  const FineXTile t = fine_x_tile(v);
+  CoefFine parts[3];
+  fine_x_warm_parts(v, t, parts);
+  double e[FS];
+  fine_x_front<true, STREAM, false>(v, t, buf + t.origin, parts, lds, e);
+  if (QP_ABL & 8) return;
+  fine_x_ends(v, t, e);
+}
+
+// sources of the x-faces (left/right) belong to columns 0 and nx-1
+__device__ __forceinline__ double fine_col_source(const FineView& vn, double an, int col) {
+  double scol = 0.0;
+  if (col == 0) scol += an * vn.other_src[0][0];
+  if (col == vn.nx - 1) scol += an * vn.other_src[0][1];
+  return scol;
+}
+
+// Middle of a y-pass on one y-chunk per lane (lane = column, register = row), shared by fine_y_body and
+// fine_fused_kernel; the ghosts gu / gd are finished.  MODE 1 / 2: the y-solve; MODE 2 stores the solution and stops.
+// MODE 0 / 1: the explicit y-operator (table cyn, weight an, column source scol), the source plane (SRC: bscale * bt),
+// and the store.  MODE 3 does nothing here.
+template <int MODE, int STREAM, bool SRC, class CoefY, class CoefYN>
+__device__ __forceinline__ void fine_y_mid(double (&e)[FS], double gu, double gd, double a, const CoefY& cy, double an,
+                                           const CoefYN& cyn, double scol, double bscale, const double* bt, double* dp,
+                                           long pitch) {
+  if (MODE == 1 || MODE == 2) {
+    e[0] = fma(a, gu, e[0]);
+    e[FS - 1] = fma(a, gd, e[FS - 1]);
+    thomas32(e, cy);
+  }
+  if (MODE == 2) {
+    fine_store_rows<STREAM>(dp, pitch, e);
+    return;
+  }
+  if (MODE != 3) {
+    explicit32(e, gu, gd, cyn, an, scol);
+    if (SRC) {
+#pragma unroll
+      for (int r = 0; r < FS; ++r) e[r] = fma(bscale, bt[(long)r * pitch], e[r]);
+    }
+    fine_store_rows<STREAM>(dp, pitch, e);
+  }
 }
 
 // y-kernel, MODE as in rect_y_kernel (0 entry, 1 carry, 2 exit, 3 reduce).  `vn` is the view whose x-solve comes next: the
@@ -316,28 +401,10 @@ __device__ __forceinline__ void fine_y_body(const FineView& v, const FineView& v
                                fine_coefs(v, 0, b, chunk_variant(2 * tx + 1, v.px), 1)};
     warm_scalar_cache(parts);
   }
-  if (MODE == 1 || MODE == 2) {
-    fine_ghost_finish(v, 1, b, ty, graw, gu, gd);
-    e[0] = fma(a, gu, e[0]);
-    e[FS - 1] = fma(a, gd, e[FS - 1]);
-    thomas32(e, cy);
-  }
-  if (MODE == 2) {
-    fine_store_rows<STREAM>(dp, v.nx, e);
-    return;
-  }
-  double scol = 0.0;                   // sources of the x-faces (left/right) belong to columns 0 and nx-1
-  if (col == 0) scol += an * vn.other_src[0][0];
-  if (col == v.nx - 1) scol += an * vn.other_src[0][1];
-  if (MODE != 3) {
-    explicit32(e, gu, gd, cyn, an, scol);
-    if (SRC) {
-      const double* bt = vn.bsrc + (long)b * ncell + (long)j0 * v.nx + col;
-#pragma unroll
-      for (int r = 0; r < FS; ++r) e[r] = fma(vn.bscale, bt[(long)r * v.nx], e[r]);
-    }
-    fine_store_rows<STREAM>(dp, v.nx, e);
-  }
+  if (MODE == 1 || MODE == 2) fine_ghost_finish(v, 1, b, ty, graw, gu, gd);
+  const double* bt = SRC ? vn.bsrc + (long)b * ncell + (long)j0 * v.nx + col : nullptr;
+  fine_y_mid<MODE, STREAM, SRC>(e, gu, gd, a, cy, an, cyn, fine_col_source(vn, an, col), vn.bscale, bt, dp, v.nx);
+  if (MODE == 2) return;
   if (QP_ABL & 8) return;
   transpose32h(e, lds, lane);          // lane = (x-chunk 2 tx + h, row j0 + (lane & 31)), register = column of the chunk
   double yf, yl;
@@ -359,4 +426,78 @@ template <int STREAM>
 __global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_y_next_kernel(FineView v, FineView vn, double* w) {
   __shared__ double lds[FINE_LDS_DOUBLES];
   fine_y_body<1, STREAM, true, true>(v, vn, w, w, lds);
+}
+
+// Fused pass F of an ADI step (qp_adi_rect_steps on a fused plan), MODE 1 carry / 2 exit, on the x-kernel tile:
+//   fine_x_front again from rhs1 (the x-solve of fine_reduce_kernel, same bits), then the y-work of fine_y_kernel<MODE> on
+//   the y-chunk every lane holds (chunk 2 ty + h of column 32 tx + c), its ghosts from the iface[1] that R left;
+//   MODE 1: explicit y-operator, rhs1' stored in place, transposed once more and the x-elimination of x-chunk tx into
+//           iface0_next (the other buffer of the x-interface pair: the neighbouring tiles still read v.iface[0]);
+//   MODE 2: the solution stored to dst.
+// One read and one write of the plane per step where the two sweeps move two of each.
+struct CoefFinePair {       // chunk p_even on lanes 0..31, chunk p_even + 1 on lanes 32..63 (tiles at the ends of a line)
+  ctab_t lo, hi;
+  bool h;
+  __device__ __forceinline__ double at(int slot, int k) const {
+    if (QP_ABL & 2) return 0.1 + 0.001 * slot;
+    const double x = lo[cidx_len(FS, slot, k)], y = hi[cidx_len(FS, slot, k)];
+    return h ? y : x;
+  }
+};
+
+// fine_ghost_finish for chunk p_even + h on half-wave h (same coefficients, same operations, per-lane selects)
+__device__ __forceinline__ void fine_ghost_finish_pair(const FineView& v, int dir, int b, int p_even, int h,
+                                                       const FineGhost& g, double& gl, double& gr) {
+  const int P = dir == 0 ? v.px : v.py;
+  const ctab_t ic = as_const(v.icoef[dir] + (long)b * (P + 1) * 3);
+  const int p = p_even + h;
+  const double l0 = h ? ic[(p_even + 1) * 3] : ic[p_even * 3];
+  const double l2 = h ? ic[(p_even + 1) * 3 + 2] : ic[p_even * 3 + 2];
+  const double r1 = h ? ic[(p_even + 2) * 3 + 1] : ic[(p_even + 1) * 3 + 1];
+  const double r2 = h ? ic[(p_even + 2) * 3 + 2] : ic[(p_even + 1) * 3 + 2];
+  gl = 0.0;
+  gr = 0.0;
+  if (p > 0) gl = fma(l0, g.q1, g.q0) * l2;
+  if (p < P - 1) gr = fma(r1, g.q2, g.q3) * r2;
+}
+
+template <int MODE, int STREAM>
+__global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_fused_kernel(FineView v, double* iface0_next, double* w,
+                                                                      double* dst) {   // dst == w in MODE 1
+  static_assert(MODE == 1 || MODE == 2, "fused pass: carry or exit");
+  __shared__ double lds[FINE_LDS_DOUBLES];
+  const int lane = threadIdx.x, h = lane >> 5, c = lane & 31;
+  FineXTile t = fine_x_tile(v);
+  const int b = t.b, tx = t.tx, ty = t.ty;
+  const int col = tx * FS + c;
+  const int yc = 2 * ty + h;           // the y-chunk of this lane after fine_x_front
+  const int va = chunk_variant(2 * ty, v.py), vb = chunk_variant(2 * ty + 1, v.py);
+  const FineGhost gyraw = fine_ghost_prefetch(v, 1, b, yc, col);
+  CoefFine parts[4];
+  parts[0] = fine_coefs(v, 0, b, chunk_variant(tx, v.px), 0);
+  parts[1] = fine_coefs(v, 1, b, va, 0);
+  parts[2] = fine_coefs(v, 1, b, vb, 0);
+  parts[3] = fine_coefs(v, 0, b, chunk_variant(tx, v.px), 1);
+  double e[FS];
+  fine_x_front<true, STREAM, false>(v, t, w + t.origin, parts, lds, e);
+  const double a = as_const(v.alpha)[b];
+  double gu, gd;
+  fine_ghost_finish_pair(v, 1, b, 2 * ty, h, gyraw, gu, gd);
+  const double scol = fine_col_source(v, a, col);
+  asm volatile("" : "+v"(t.off));
+  double* dp = dst + t.origin + t.off;
+  if (va == vb) {                      // wave-uniform: interior tile rows
+    fine_y_mid<MODE, STREAM, false>(e, gu, gd, a, parts[1], a, parts[1], scol, 0.0, nullptr, dp, v.nx);
+  } else {
+    const CoefFinePair cy{parts[1].part, parts[2].part, h != 0};
+    fine_y_mid<MODE, STREAM, false>(e, gu, gd, a, cy, a, cy, scol, 0.0, nullptr, dp, v.nx);
+  }
+  if (MODE == 2) return;
+  if (QP_ABL & 8) return;
+  transpose32h(e, lds, lane);          // lane = row 64 ty + lane, register = column of x-chunk tx
+  double yf, yl;
+  ends32(e, parts[3], yf, yl);
+  double* ir = iface0_next + (long)b * (2 * v.px + 2) * v.ny + ty * 64 + lane;
+  ir[(long)(2 * tx + 1) * v.ny] = yf;
+  ir[(long)(2 * tx + 2) * v.ny] = yl;
 }
