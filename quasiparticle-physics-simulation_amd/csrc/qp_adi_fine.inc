@@ -238,12 +238,26 @@ __device__ __forceinline__ FineXTile fine_x_tile(const FineView& v) {
   return t;
 }
 
+// sources of the y-faces (up/down) belong to rows 0 and ny-1
+__device__ __forceinline__ double fine_row_source(const FineView& v, double a, int row) {
+  double srow = 0.0;
+  if (row == 0) srow += a * v.other_src[1][0];
+  if (row == v.ny - 1) srow += a * v.other_src[1][1];
+  return srow;
+}
+
+struct FineNoHook {
+  __device__ __forceinline__ void operator()() const {}
+};
+
 // Front half of every x-kernel tile: x-solve from rhs1 at `tile`, explicit x-operator (EXPLICIT), source plane (SRC), and
 // the transpose back - on return lane (h, c) holds y-chunk 2 ty + h of column 32 tx + c, register r = row 64 ty + 32 h + r.
-// parts[0] is the x-solve table; every part is warmed in the scalar cache while the rows are in flight.
-template <bool EXPLICIT, int STREAM, bool SRC, int NPART>
+// parts[0] is the x-solve table; every part is warmed in the scalar cache while the rows are in flight.  `hook` runs right
+// after the row loads are issued (work on values loaded before them, without waiting for the rows).
+template <bool EXPLICIT, int STREAM, bool SRC, int NPART, class Hook = FineNoHook>
 __device__ __forceinline__ void fine_x_front(const FineView& v, const FineXTile& t, const double* tile,
-                                             const CoefFine (&parts)[NPART], double* lds, double (&e)[FS]) {
+                                             const CoefFine (&parts)[NPART], double* lds, double (&e)[FS],
+                                             const Hook& hook = Hook()) {
   const int lane = threadIdx.x;
   const int tx = t.tx, ty = t.ty, b = t.b;
   const unsigned off = t.off;
@@ -254,15 +268,14 @@ __device__ __forceinline__ void fine_x_front(const FineView& v, const FineXTile&
   const CoefFine cx = parts[0];
   fine_load_rows<STREAM>(tile + off, v.nx, e);
   warm_scalar_cache(parts);
+  hook();
   transpose32h(e, lds, lane);
   double gl, gr;
   fine_ghost_finish(v, 0, b, tx, graw, gl, gr);
   e[0] = fma(a, gl, e[0]);
   e[FS - 1] = fma(a, gr, e[FS - 1]);
   thomas32(e, cx);
-  double srow = 0.0;                   // sources of the y-faces (up/down) belong to rows 0 and ny-1
-  if (row == 0) srow += a * v.other_src[1][0];
-  if (row == v.ny - 1) srow += a * v.other_src[1][1];
+  const double srow = fine_row_source(v, a, row);
   if (EXPLICIT) explicit32(e, gl, gr, cx, a, srow);
   double bv[SRC ? FS : 1];
   if (SRC) {                           // the source tile, in the storage layout: issued here, consumed after the transpose
@@ -277,12 +290,12 @@ __device__ __forceinline__ void fine_x_front(const FineView& v, const FineXTile&
   }
 }
 
-// y-elimination of the two y-chunks the x-kernel tile holds after fine_x_front -> iface[1]
-__device__ __forceinline__ void fine_x_ends(const FineView& v, const FineXTile& t, const double (&e)[FS]) {
+// y-elimination of the two y-chunks the x-kernel tile holds after fine_x_front -> iface1 (in the layout of v.iface[1])
+__device__ __forceinline__ void fine_x_ends(const FineView& v, const FineXTile& t, const double (&e)[FS], double* iface1) {
   const int lane = threadIdx.x, h = lane >> 5, c = lane & 31;
   double yf, yl;
   ends32_pair(e, v, 1, t.b, 2 * t.ty, v.py, h, yf, yl);
-  double* ir = v.iface[1] + (long)t.b * (2 * v.py + 2) * v.nx + t.tx * FS + c;
+  double* ir = iface1 + (long)t.b * (2 * v.py + 2) * v.nx + t.tx * FS + c;
   const int yc = 2 * t.ty + h;
   ir[(long)(2 * yc + 1) * v.nx] = yf;
   ir[(long)(2 * yc + 2) * v.nx] = yl;
@@ -307,7 +320,7 @@ __global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_x_kernel(FineView v, do
   asm volatile("" : "+v"(t.off));      // the 32 row addresses are formed again here instead of living through the solve
   fine_store_rows<STREAM>(tile + t.off, v.nx, e);
   if (QP_ABL & 8) return;
-  fine_x_ends(v, t, e);
+  fine_x_ends(v, t, e, v.iface[1]);
 }
 
 // Reduce pass R of a fused ADI step (qp_adi_rect_steps): the x-kernel without its plane store - rhs1 is only read, and
@@ -322,7 +335,7 @@ __global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_reduce_kernel(FineView 
   double e[FS];
   fine_x_front<true, STREAM, false>(v, t, buf + t.origin, parts, lds, e);
   if (QP_ABL & 8) return;
-  fine_x_ends(v, t, e);
+  fine_x_ends(v, t, e, v.iface[1]);
 }
 
 // sources of the x-faces (left/right) belong to columns 0 and nx-1
@@ -461,25 +474,75 @@ __device__ __forceinline__ void fine_ghost_finish_pair(const FineView& v, int di
   if (p < P - 1) gr = fma(r1, g.q2, g.q3) * r2;
 }
 
-template <int MODE, int STREAM>
-__global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_fused_kernel(FineView v, double* iface0_next, double* w,
-                                                                      double* dst) {   // dst == w in MODE 1
+// One-pass steps (fine_steps_onepass, DESIGN.md 2.2).  The x-front is linear in the two x-ghosts, so the y-interface rows
+// of the next step are P + phi_L[c] S_gl + phi_R[c] S_gr: P is the x-front and y-elimination of rhs1' with zero x-ghosts,
+// formed by the one-pass kernel from the rhs1' it holds; S are the y-eliminations of the ghosts themselves, four scalars
+// per (field, x-chunk, y-chunk) that fine_ghostsum_kernel forms once the x-interface rows of the next step exist.
+struct FineOnePass {
+  const double* phi;     // [nfield][3 x-chunk variants][2][FS]: x-front response of column c to gl = 1 (phi_L), gr = 1 (phi_R)
+  const double* sums;    // [nfield][px][py][4] S = (ends_f gl, ends_l gl, ends_f gr, ends_l gr) of this step (zeros: none)
+  double* p_next;        // P of the next step, in the layout of iface[1]
+};
+
+// what q0..q3 of y-chunk yc at column c of x-chunk tx add to P: phi_L / phi_R of the column and S of the chunks yc - 1
+// (last entry), yc (both) and yc + 1 (first entry)
+struct FineGhostSums {
+  double fl, fr, s[8];
+};
+
+__device__ __forceinline__ FineGhostSums fine_ghost_sums_prefetch(const FineView& v, const FineOnePass& op, int b, int tx,
+                                                                  int yc, int c) {
+  FineGhostSums r;
+  const double* ph = op.phi + ((long)b * 3 + chunk_variant(tx, v.px)) * 2 * FS + c;
+  r.fl = ph[0];
+  r.fr = ph[FS];
+  const double* s = op.sums + (((long)b * v.px + tx) * v.py + yc) * 4;
+  const double* sa = s + (yc > 0 ? -4 : 0);              // clamped at the ends of a column: rows 0 and 2 py + 1 take none
+  const double* sb = s + (yc < v.py - 1 ? 4 : 0);
+  r.s[0] = sa[1];
+  r.s[1] = sa[3];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r.s[2 + i] = s[i];
+  r.s[6] = sb[0];
+  r.s[7] = sb[2];
+  return r;
+}
+
+// q0..q3 in P form -> the y-reduced right-hand sides (rows 0 and 2 py + 1 hold zeros and keep them)
+__device__ __forceinline__ void fine_ghost_correct(const FineView& v, int yc, const FineGhostSums& r, FineGhost& g) {
+  if (yc > 0) g.q0 = fma(r.fl, r.s[0], fma(r.fr, r.s[1], g.q0));
+  g.q1 = fma(r.fl, r.s[2], fma(r.fr, r.s[4], g.q1));
+  g.q2 = fma(r.fl, r.s[3], fma(r.fr, r.s[5], g.q2));
+  if (yc < v.py - 1) g.q3 = fma(r.fl, r.s[6], fma(r.fr, r.s[7], g.q3));
+}
+
+// The fused pass, and with ONEPASS its one-pass form F': the y-ghosts come from v.iface[1] in P form and op.sums (all
+// zeros on the first step, whose rows R left in full), and MODE 1 also forms P of the next step from the rhs1' it holds,
+// after the plane store (the x-front of fine_x_front with zero x-ghosts, without the load, and fine_x_ends) -> op.p_next.
+template <int MODE, int STREAM, bool ONEPASS>
+__device__ __forceinline__ void fine_fused_body(const FineView& v, double* iface0_next, double* w, double* dst,
+                                                const FineOnePass& op, double* lds) {
   static_assert(MODE == 1 || MODE == 2, "fused pass: carry or exit");
-  __shared__ double lds[FINE_LDS_DOUBLES];
   const int lane = threadIdx.x, h = lane >> 5, c = lane & 31;
   FineXTile t = fine_x_tile(v);
   const int b = t.b, tx = t.tx, ty = t.ty;
   const int col = tx * FS + c;
   const int yc = 2 * ty + h;           // the y-chunk of this lane after fine_x_front
   const int va = chunk_variant(2 * ty, v.py), vb = chunk_variant(2 * ty + 1, v.py);
-  const FineGhost gyraw = fine_ghost_prefetch(v, 1, b, yc, col);
+  FineGhost gyraw = fine_ghost_prefetch(v, 1, b, yc, col);
+  FineGhostSums gs{};
+  if (ONEPASS) gs = fine_ghost_sums_prefetch(v, op, b, tx, yc, c);
   CoefFine parts[4];
   parts[0] = fine_coefs(v, 0, b, chunk_variant(tx, v.px), 0);
   parts[1] = fine_coefs(v, 1, b, va, 0);
   parts[2] = fine_coefs(v, 1, b, vb, 0);
   parts[3] = fine_coefs(v, 0, b, chunk_variant(tx, v.px), 1);
   double e[FS];
-  fine_x_front<true, STREAM, false>(v, t, w + t.origin, parts, lds, e);
+  if (ONEPASS) {     // the correction waits for the sums only, not for the rows
+    fine_x_front<true, STREAM, false>(v, t, w + t.origin, parts, lds, e, [&]() { fine_ghost_correct(v, yc, gs, gyraw); });
+  } else {
+    fine_x_front<true, STREAM, false>(v, t, w + t.origin, parts, lds, e);
+  }
   const double a = as_const(v.alpha)[b];
   double gu, gd;
   fine_ghost_finish_pair(v, 1, b, 2 * ty, h, gyraw, gu, gd);
@@ -500,4 +563,46 @@ __global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_fused_kernel(FineView v
   double* ir = iface0_next + (long)b * (2 * v.px + 2) * v.ny + ty * 64 + lane;
   ir[(long)(2 * tx + 1) * v.ny] = yf;
   ir[(long)(2 * tx + 2) * v.ny] = yl;
+  if (ONEPASS) {     // P of the next step
+    thomas32(e, parts[0]);
+    explicit32(e, 0.0, 0.0, parts[0], a, fine_row_source(v, a, ty * 64 + lane));
+    transpose32h(e, lds, lane);
+    fine_x_ends(v, t, e, op.p_next);
+  }
+}
+
+template <int MODE, int STREAM>
+__global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_fused_kernel(FineView v, double* iface0_next, double* w,
+                                                                      double* dst) {   // dst == w in MODE 1
+  __shared__ double lds[FINE_LDS_DOUBLES];
+  fine_fused_body<MODE, STREAM, false>(v, iface0_next, w, dst, FineOnePass{}, lds);
+}
+
+// One-pass step F' (MODE 1) and the exit pass of one-pass steps (MODE 2)
+template <int MODE, int STREAM>
+__global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_onepass_kernel(FineView v, double* iface0_next, double* w,
+                                                                        double* dst, FineOnePass op) {
+  __shared__ double lds[FINE_LDS_DOUBLES];
+  fine_fused_body<MODE, STREAM, true>(v, iface0_next, w, dst, op, lds);
+}
+
+// Ghost-sum pass X of the one-pass steps, on the x-kernel tile (fine_block: the XCD that wrote most of the rows it reads):
+// lane = row 64 ty + lane forms gl / gr of x-chunk tx from v.iface[0] as fine_x_front does, and each half-wave reduces
+// them against the first / last rows of A_y^-1 of its y-chunk 2 ty + h (wy: [nfield][3 y-chunk variants][2][FS],
+// fine_plan_prepare) -> S = (ends_f gl, ends_l gl, ends_f gr, ends_l gr) of (field, tx, 2 ty + h).
+__global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_ghostsum_kernel(FineView v, const double* wy, double* sums) {
+  const int lane = threadIdx.x, h = lane >> 5, k = lane & 31;
+  const FineXTile t = fine_x_tile(v);
+  const int yc = 2 * t.ty + h;
+  const FineGhost g = fine_ghost_prefetch(v, 0, t.b, t.tx, t.ty * 64 + lane);
+  const double* wr = wy + ((long)t.b * 3 + chunk_variant(yc, v.py)) * 2 * FS + k;
+  const double wf = wr[0], wl = wr[FS];
+  double gl, gr;
+  fine_ghost_finish(v, 0, t.b, t.tx, g, gl, gr);
+  double s[4] = {wf * gl, wl * gl, wf * gr, wl * gr};
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] += __shfl_xor(s[i], m);
+  if (k < 4) sums[(((long)t.b * v.px + t.tx) * v.py + yc) * 4 + k] = k == 0 ? s[0] : k == 1 ? s[1] : k == 2 ? s[2] : s[3];
 }

@@ -502,7 +502,7 @@ static double reduced_tables(const DirSpec& s, double a, int p0, int Ploc, doubl
     else hipLaunchKernelGGL((NAME<ARG, 3>), __VA_ARGS__);                          \
   } while (0)
 
-#define QP_LAUNCH_FINE_SRC(mode, NAME, ARG, ...)                                   \
+#define QP_LAUNCH_FINE_SRC(mode, NAME, ARG, ...)                                \
   do {                                                                             \
     if ((mode) == 0) hipLaunchKernelGGL((NAME<ARG, 0, true>), __VA_ARGS__);        \
     else if ((mode) == 2) hipLaunchKernelGGL((NAME<ARG, 2, true>), __VA_ARGS__);   \
@@ -518,10 +518,15 @@ struct qp_adi_rect_plan {
   double* d_fctab = nullptr;
   double* d_ficoef[2] = {nullptr, nullptr};
   double* d_fiface[2] = {nullptr, nullptr};
-  // fused steps (qp_adi_rect_steps): reduce pass + fused pass per step, the x-interface rows ping-pong between
-  // d_fiface[0] and d_fiface0_next (the fused pass writes the rows its neighbours are still reading)
-  bool fused = false;
+  // fused steps (qp_adi_rect_steps): 1 = reduce pass + fused pass per step, 2 = one-pass steps (fine_steps_onepass); the
+  // x-interface rows ping-pong between d_fiface[0] and d_fiface0_next (the fused pass writes the rows its neighbours are
+  // still reading), and on one-pass plans the y-interface rows in P form between d_fiface[1] and d_fiface1_next
+  int fused = 0;
   double* d_fiface0_next = nullptr;
+  double* d_fiface1_next = nullptr;
+  double* d_fphi = nullptr;      // [nfield][3 x-chunk variants][2][FS] (FineOnePass::phi)
+  double* d_fwy = nullptr;       // [nfield][3 y-chunk variants][2][FS] first / last rows of A_y^-1 (fine_ghostsum_kernel)
+  double* d_fsums = nullptr;     // [2][nfield][px][py][4] ghost sums S: [0] stays zero (first step), [1] fine_ghostsum_kernel
   double* d_alpha = nullptr;
   double* d_tab = nullptr;
   double* d_ctab = nullptr;
@@ -698,16 +703,55 @@ static bool fine_tiles_allowed() {      // QPSIM_FINE_TILES=0 switches the fine 
   return !e || atoi(e) != 0;
 }
 
-// Fused ADI steps on fine plans: 24 instead of 32 B of plane traffic per cell-update.  QPSIM_ADI_FUSED=0 / 1
-// forces the choice (1: on every fine plan); the default is the size rule measured on MI355X (ms per step, two sweeps /
-// fused): 4096^2 0.094 / 0.080, 1024^2 x 12 0.232 / 0.225 (c2), 2048^2 0.0262 / 0.0259 - but 1024^2 0.0125 / 0.0135: below
-// 4 Mi cells the fused pass's longer serial stretch per tile is exposed (2 tiles per SIMD) and the bytes saved are cheap.
+// Fused ADI steps on fine plans: 0 two sweeps, 1 reduce + fused pass (24 instead of 32 B of plane traffic
+// per cell-update), 2 one-pass steps (16 B after the first step).  QPSIM_ADI_FUSED=0 / 1 / 2 forces the choice (1 and 2: on
+// every fine plan; any other non-zero value means 1).  The default is the size rule measured on MI355X (ms per step, two
+// sweeps / reduce + fused): 4096^2 0.094 / 0.080, 1024^2 x 12 0.232 / 0.225 (c2), 2048^2 0.0262 / 0.0259 - but 1024^2
+// 0.0125 / 0.0135: below 4 Mi cells the fused pass's longer serial stretch per tile is exposed (2 tiles per SIMD) and the
+// bytes saved are cheap.  Where fused steps run, the one-pass form replaces them (see DESIGN.md for its A/B).
 // Only plain step plans: Peaceman-Rachford plans never run steps.
-static bool fine_fused_wanted(const qp_adi_rect_plan* plan) {
-  if (plan->pr_scale != 0.0) return false;
-  if (const char* e = getenv("QPSIM_ADI_FUSED")) return atoi(e) != 0;
+static int fine_fused_wanted(const qp_adi_rect_plan* plan) {
+  if (plan->pr_scale != 0.0) return 0;
+  if (const char* e = getenv("QPSIM_ADI_FUSED")) {
+    const int m = atoi(e);
+    return m == 0 ? 0 : m == 2 ? 2 : 1;
+  }
   const FineView& f = plan->fview;
-  return (long)f.nfield * f.ny * f.nx >= 4L * 1024 * 1024;
+  return (long)f.nfield * f.ny * f.nx >= 4L * 1024 * 1024 ? 2 : 0;
+}
+
+// One-pass tables of a chunk (fine_plan_prepare, from the table entries the kernels read):
+// x-chunk: phi_L / phi_R = the x-front (fine_x_front without its sources) of a unit left / right x-ghost;
+static void fine_ghost_response(const double* tab, double a, double* phi) {       // phi[2][FS]
+  for (int side = 0; side < 2; ++side) {
+    double e[FS] = {};
+    e[side ? FS - 1 : 0] = a;
+    double dp = 0.0;
+    for (int k = 0; k < FS; ++k) {
+      dp = std::fma(tab[T_AWF * FS + k], dp, e[k] * tab[T_W * FS + k]);
+      e[k] = dp;
+    }
+    double x = 0.0;
+    for (int k = FS - 1; k >= 0; --k) {
+      x = std::fma(tab[T_AWB * FS + k], x, e[k]);
+      e[k] = x;
+    }
+    double prev = side ? 0.0 : 1.0;
+    for (int k = 0; k < FS; ++k) {
+      const double cur = e[k];
+      const double nxt = k + 1 < FS ? e[k + 1] : (side ? 1.0 : 0.0);
+      phi[side * FS + k] = std::fma(a, prev + nxt, tab[T_C0 * FS + k] * cur);
+      prev = cur;
+    }
+  }
+}
+
+// y-chunk: the weights of ends32 (scaled eliminations), ends_f(e) = sum_k w[0][k] e_k, ends_l(e) = sum_k w[1][k] e_k
+static void fine_end_rows(const double* tab, double* w) {       // w[2][FS]
+  w[0] = tab[T_EV * FS];
+  for (int k = 1; k < FS; ++k) w[k] = w[k - 1] * tab[T_EAV * FS + k - 1];
+  w[FS + FS - 1] = tab[T_EW * FS + FS - 1];
+  for (int k = FS - 2; k >= 0; --k) w[FS + k] = w[FS + k + 1] * tab[T_EAWF * FS + k + 1];
 }
 
 static bool fine_tiles_wanted(int nfield, int ny, int nx) {
@@ -737,6 +781,12 @@ static void fine_plan_prepare(qp_adi_rect_plan* plan, double r, const double* dc
   std::vector<double> ctab((size_t)2 * nfield * 4 * 2 * CT_PART, 0.0);
   std::vector<double> icoef[2];
   for (int d = 0; d < 2; ++d) icoef[d].assign((size_t)nfield * (spec[d].P + 1) * 3, 0.0);
+  const int fused = fine_fused_wanted(plan);
+  std::vector<double> phi, wy;            // one-pass tables per (field, variant): x-ghost responses, A_y^-1 end rows
+  if (fused == 2) {
+    phi.assign((size_t)nfield * 3 * 2 * FS, 0.0);
+    wy.assign((size_t)nfield * 3 * 2 * FS, 0.0);
+  }
   for (int b = 0; b < nfield; ++b) {
     const double a = r * dcoef_host[b];
     for (int d = 0; d < 2; ++d) {
@@ -760,6 +810,11 @@ static void fine_plan_prepare(qp_adi_rect_plan* plan, double r, const double* dc
         }
         if (!table_is_compact_len(FS, tab.data())) return;
         build_compact_table_len(FS, tab.data(), &ctab[(((size_t)d * nfield + b) * 4 + var) * 2 * CT_PART]);
+        if (fused == 2) {
+          const size_t o = ((size_t)b * 3 + var) * 2 * FS;
+          if (d == 0) fine_ghost_response(tab.data(), a, &phi[o]);
+          else fine_end_rows(tab.data(), &wy[o]);
+        }
       }
       const double far = reduced_tables(spec[d], a, 0, P, nullptr, &icoef[d][(size_t)b * (P + 1) * 3], FS);
       if (!(far < kFarCouplingDrop)) return;
@@ -771,8 +826,14 @@ static void fine_plan_prepare(qp_adi_rect_plan* plan, double r, const double* dc
     slab.upload_owned(std::move(icoef[d]), &plan->d_ficoef[d]);
     slab.zeros((size_t)nfield * (2 * spec[d].P + 2) * nlines, &plan->d_fiface[d]);
   }
-  plan->fused = fine_fused_wanted(plan);
-  if (plan->fused) slab.zeros((size_t)nfield * (2 * spec[0].P + 2) * ny, &plan->d_fiface0_next);
+  plan->fused = fused;
+  if (fused) slab.zeros((size_t)nfield * (2 * spec[0].P + 2) * ny, &plan->d_fiface0_next);
+  if (fused == 2) {
+    slab.upload_owned(std::move(phi), &plan->d_fphi);
+    slab.upload_owned(std::move(wy), &plan->d_fwy);
+    slab.zeros((size_t)nfield * (2 * spec[1].P + 2) * nx, &plan->d_fiface1_next);
+    slab.zeros((size_t)2 * nfield * spec[0].P * spec[1].P * 4, &plan->d_fsums);
+  }
   f.bsrc = nullptr;
   f.bscale = 0.0;
   plan->fine = true;      // the view's pointers are bound after SlabBuilder::commit (rect_plan_create_impl)
@@ -826,6 +887,42 @@ static int fine_steps_fused(qp_adi_rect_plan* plan, double* u, int nsteps, hipSt
     else QP_LAUNCH_FINE(f.stream, fine_fused_kernel, 2, dim3(tiles), dim3(64), 0, stream, f, next, w, u);
   }
   return check_launch("qp_adi_rect_steps (fused fine tiles)");
+}
+
+// qp_adi_rect_steps on a one-pass plan: ENTRY, R of the first step, then per step one plane pass - F' (fine_onepass_kernel
+// <1>: the fused pass plus P of the next step's y-interface rows) and the small ghost-sum pass X of the next step, and on
+// the last step the exit form of F'.  Step s reads the x-interface rows from ix[s % 2] and the y-interface rows from
+// iy[s % 2] (full rows after R on step 0, with the all-zero sums; P form after that), and writes buffer (s + 1) % 2 of both.
+static int fine_steps_onepass(qp_adi_rect_plan* plan, double* u, int nsteps, hipStream_t stream) {
+  FineView f = plan->fview;
+  const unsigned tiles = (unsigned)((long)f.nfield * (f.ny / 64) * f.px);
+  double* w = plan->d_work;
+  double* const ix[2] = {plan->d_fiface[0], plan->d_fiface0_next};
+  double* const iy[2] = {plan->d_fiface[1], plan->d_fiface1_next};
+  double* const sums = plan->d_fsums + (size_t)f.nfield * f.px * f.py * 4;
+  FineOnePass op{plan->d_fphi, nullptr, nullptr};
+  f.iface[0] = ix[0];
+  f.iface[1] = iy[0];
+  QP_LAUNCH_FINE(f.stream, fine_y_kernel, 0, dim3(tiles), dim3(64), 0, stream, f, (const double*)u, w);
+  if (f.stream == 0) hipLaunchKernelGGL((fine_reduce_kernel<0>), dim3(tiles), dim3(64), 0, stream, f, (const double*)w);
+  else if (f.stream == 2) hipLaunchKernelGGL((fine_reduce_kernel<2>), dim3(tiles), dim3(64), 0, stream, f, (const double*)w);
+  else hipLaunchKernelGGL((fine_reduce_kernel<3>), dim3(tiles), dim3(64), 0, stream, f, (const double*)w);
+  for (int s = 0; s < nsteps; ++s) {
+    f.iface[0] = ix[s & 1];
+    f.iface[1] = iy[s & 1];
+    double* next = ix[(s + 1) & 1];
+    op.p_next = iy[(s + 1) & 1];
+    op.sums = s == 0 ? plan->d_fsums : sums;
+    if (s + 1 < nsteps) {
+      QP_LAUNCH_FINE(f.stream, fine_onepass_kernel, 1, dim3(tiles), dim3(64), 0, stream, f, next, w, w, op);
+      FineView fx = f;
+      fx.iface[0] = next;
+      hipLaunchKernelGGL(fine_ghostsum_kernel, dim3(tiles), dim3(64), 0, stream, fx, (const double*)plan->d_fwy, sums);
+    } else {
+      QP_LAUNCH_FINE(f.stream, fine_onepass_kernel, 2, dim3(tiles), dim3(64), 0, stream, f, next, w, u, op);
+    }
+  }
+  return check_launch("qp_adi_rect_steps (one-pass fine tiles)");
 }
 
 int rect_ablation_mask() { return QP_ABL; }
@@ -1143,6 +1240,7 @@ int qp_adi_rect_steps(qp_adi_rect_plan* plan, double* u, int32_t nsteps, void* s
   QP_REQUIRE(plan && u, "plan and u must be non-NULL");
   QP_REQUIRE(nsteps >= 1, "nsteps must be >= 1");
   QP_REQUIRE(!plan->decomposed, "a decomposed plan needs halo exchanges between phases: drive it with qp_adi_rect_phase");
+  if (plan->fine && plan->fused == 2) return qp::fine_steps_onepass(plan, u, nsteps, (hipStream_t)stream);
   if (plan->fine && plan->fused) return qp::fine_steps_fused(plan, u, nsteps, (hipStream_t)stream);
   int rc = qp_adi_rect_phase(plan, QP_ADI_ENTRY, u, stream);
   for (int s = 0; s < nsteps && rc == QP_OK; ++s) {

@@ -7,8 +7,9 @@ Pauli guard is reduced per member on the device (``qp_pauli_stats_members`` and 
 so every member warns and raises exactly as its lone run would, its messages prefixed ``member m: ``.
 
 Rounding: members are bit-equal to their lone ``run_2d_crank_nicolson`` call with ``diffusion_scheme="adi"`` when both use
-the same ADI tile family (``QPSIM_FINE_TILES``), within 2e-13 relative otherwise, and within 1e-12 relative with
-``cn_exact`` (the iteration's stop test is global over the batch).
+the same ADI tile family (``QPSIM_FINE_TILES``) and the same step form (``QPSIM_ADI_FUSED``: a batch of at least 4 Mi
+cells takes the one-pass steps, which round the interface rows differently, while a smaller lone member does not), within
+2e-13 relative otherwise, and within 1e-12 relative with ``cn_exact`` (the iteration's stop test is global over the batch).
 """
 from __future__ import annotations
 
