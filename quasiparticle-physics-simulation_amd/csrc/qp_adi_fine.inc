@@ -477,11 +477,15 @@ __device__ __forceinline__ void fine_ghost_finish_pair(const FineView& v, int di
 // One-pass steps (fine_steps_onepass, DESIGN.md 2.2).  The x-front is linear in the two x-ghosts, so the y-interface rows
 // of the next step are P + phi_L[c] S_gl + phi_R[c] S_gr: P is the x-front and y-elimination of rhs1' with zero x-ghosts,
 // formed by the one-pass kernel from the rhs1' it holds; S are the y-eliminations of the ghosts themselves, four scalars
-// per (field, x-chunk, y-chunk) that fine_ghostsum_kernel forms once the x-interface rows of the next step exist.
+// per (field, x-chunk, y-chunk).  The ghosts are linear in the x-interface values yf / yl, so every tile leaves the
+// y-eliminations T of the yf / yl it has just formed (fine_tile_sums, while they are in registers) and
+// fine_ghostsum_kernel combines the T of an x-chunk and its two neighbours into S once all tiles are done.
 struct FineOnePass {
   const double* phi;     // [nfield][3 x-chunk variants][2][FS]: x-front response of column c to gl = 1 (phi_L), gr = 1 (phi_R)
   const double* sums;    // [nfield][px][py][4] S = (ends_f gl, ends_l gl, ends_f gr, ends_l gr) of this step (zeros: none)
   double* p_next;        // P of the next step, in the layout of iface[1]
+  const double* wy;      // [nfield][3 y-chunk variants][2][FS] first / last rows of A_y^-1 (fine_plan_prepare)
+  double* tsums;         // [nfield][px][py][4] T = (ends_f yf, ends_l yf, ends_f yl, ends_l yl) of the next step's x-rows
 };
 
 // what q0..q3 of y-chunk yc at column c of x-chunk tx add to P: phi_L / phi_R of the column and S of the chunks yc - 1
@@ -516,9 +520,30 @@ __device__ __forceinline__ void fine_ghost_correct(const FineView& v, int yc, co
   if (yc < v.py - 1) g.q3 = fma(r.fl, r.s[6], fma(r.fr, r.s[7], g.q3));
 }
 
+// T of (field b, x-chunk tx, y-chunk yc = 2 ty + h): lane = row 64 ty + lane holds yf / yl of its row and the weights
+// wf / wl of row k = lane & 31 of its y-chunk.  The four products are summed over each half-wave by the 5-level xor
+// butterfly in its halving form: at distance 16 a lane keeps the two sums its bit 4 selects and hands the other two over,
+// at distance 8 likewise one of two by bit 3 - the same pairwise additions in the same tree, 6 shuffles instead of 20 -
+// and every lane of the group k / 8 = i ends with entry i.  All eight store it (one address per group, the same value): a
+// store under a lane mask costs the one-pass kernel its third wave per SIMD (see fine_onepass_kernel).
+__device__ __forceinline__ void fine_tile_sums(const FineView& v, int b, int tx, int yc, int k, double wf, double wl,
+                                               double yf, double yl, double* tsums) {
+  const bool hi16 = (k & 16) != 0, hi8 = (k & 8) != 0;
+  const double s0 = wf * yf, s1 = wl * yf, s2 = wf * yl, s3 = wl * yl;
+  double a0 = hi16 ? s2 : s0, a1 = hi16 ? s3 : s1;
+  a0 += __shfl_xor(hi16 ? s0 : s2, 16);
+  a1 += __shfl_xor(hi16 ? s1 : s3, 16);
+  double a = hi8 ? a1 : a0;
+  a += __shfl_xor(hi8 ? a0 : a1, 8);
+#pragma unroll
+  for (int m = 4; m >= 1; m >>= 1) a += __shfl_xor(a, m);
+  tsums[(((long)b * v.px + tx) * v.py + yc) * 4 + (k >> 3)] = a;
+}
+
 // The fused pass, and with ONEPASS its one-pass form F': the y-ghosts come from v.iface[1] in P form and op.sums (all
 // zeros on the first step, whose rows R left in full), and MODE 1 also forms P of the next step from the rhs1' it holds,
-// after the plane store (the x-front of fine_x_front with zero x-ghosts, without the load, and fine_x_ends) -> op.p_next.
+// after the plane store (the x-front of fine_x_front with zero x-ghosts, without the load, and fine_x_ends) -> op.p_next,
+// and T of the x-interface rows it writes (fine_tile_sums) -> op.tsums.
 template <int MODE, int STREAM, bool ONEPASS>
 __device__ __forceinline__ void fine_fused_body(const FineView& v, double* iface0_next, double* w, double* dst,
                                                 const FineOnePass& op, double* lds) {
@@ -557,13 +582,20 @@ __device__ __forceinline__ void fine_fused_body(const FineView& v, double* iface
   }
   if (MODE == 2) return;
   if (QP_ABL & 8) return;
+  double wf = 0.0, wl = 0.0;           // row c of the end rows of y-chunk yc: in flight during the transpose and ends32
+  if (ONEPASS) {
+    const double* wr = op.wy + ((long)b * 3 + (h ? vb : va)) * 2 * FS + c;
+    wf = wr[0];
+    wl = wr[FS];
+  }
   transpose32h(e, lds, lane);          // lane = row 64 ty + lane, register = column of x-chunk tx
   double yf, yl;
   ends32(e, parts[3], yf, yl);
   double* ir = iface0_next + (long)b * (2 * v.px + 2) * v.ny + ty * 64 + lane;
   ir[(long)(2 * tx + 1) * v.ny] = yf;
   ir[(long)(2 * tx + 2) * v.ny] = yl;
-  if (ONEPASS) {     // P of the next step
+  if (ONEPASS) {     // T of these rows, then P of the next step
+    fine_tile_sums(v, b, tx, yc, c, wf, wl, yf, yl, op.tsums);
     thomas32(e, parts[0]);
     explicit32(e, 0.0, 0.0, parts[0], a, fine_row_source(v, a, ty * 64 + lane));
     transpose32h(e, lds, lane);
@@ -578,31 +610,45 @@ __global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_fused_kernel(FineView v
   fine_fused_body<MODE, STREAM, false>(v, iface0_next, w, dst, FineOnePass{}, lds);
 }
 
-// One-pass step F' (MODE 1) and the exit pass of one-pass steps (MODE 2)
+// One-pass step F' (MODE 1) and the exit pass of one-pass steps (MODE 2).  F' with the tile sums sits at the edge of three
+// waves per SIMD (168 VGPRs): left to itself the scheduler gives the third wave up (174 VGPRs); held to three it
+// allocates 159 without scratch.  The exit pass (132 VGPRs) is not affected.
+#ifdef QP_FORCE_WAVES
+#define QP_ONEPASS_WAVES_ATTR QP_WAVES_ATTR
+#else
+#define QP_ONEPASS_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(3)))
+#endif
 template <int MODE, int STREAM>
-__global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_onepass_kernel(FineView v, double* iface0_next, double* w,
+__global__ void __launch_bounds__(64) QP_ONEPASS_WAVES_ATTR fine_onepass_kernel(FineView v, double* iface0_next, double* w,
                                                                         double* dst, FineOnePass op) {
   __shared__ double lds[FINE_LDS_DOUBLES];
   fine_fused_body<MODE, STREAM, true>(v, iface0_next, w, dst, op, lds);
 }
 
-// Ghost-sum pass X of the one-pass steps, on the x-kernel tile (fine_block: the XCD that wrote most of the rows it reads):
-// lane = row 64 ty + lane forms gl / gr of x-chunk tx from v.iface[0] as fine_x_front does, and each half-wave reduces
-// them against the first / last rows of A_y^-1 of its y-chunk 2 ty + h (wy: [nfield][3 y-chunk variants][2][FS],
-// fine_plan_prepare) -> S = (ends_f gl, ends_l gl, ends_f gr, ends_l gr) of (field, tx, 2 ty + h).
-__global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_ghostsum_kernel(FineView v, const double* wy, double* sums) {
-  const int lane = threadIdx.x, h = lane >> 5, k = lane & 31;
-  const FineXTile t = fine_x_tile(v);
-  const int yc = 2 * t.ty + h;
-  const FineGhost g = fine_ghost_prefetch(v, 0, t.b, t.tx, t.ty * 64 + lane);
-  const double* wr = wy + ((long)t.b * 3 + chunk_variant(yc, v.py)) * 2 * FS + k;
-  const double wf = wr[0], wl = wr[FS];
-  double gl, gr;
-  fine_ghost_finish(v, 0, t.b, t.tx, g, gl, gr);
-  double s[4] = {wf * gl, wl * gl, wf * gr, wl * gr};
-#pragma unroll
-  for (int m = 16; m >= 1; m >>= 1)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s[i] += __shfl_xor(s[i], m);
-  if (k < 4) sums[(((long)t.b * v.px + t.tx) * v.py + yc) * 4 + k] = k == 0 ? s[0] : k == 1 ? s[1] : k == 2 ? s[2] : s[3];
+// Ghost-sum pass X of the one-pass steps: one thread per (field, x-chunk tx, y-chunk q) combines T of tx - 1, tx and
+// tx + 1 (fine_tile_sums of the pass before) into S = (ends_f gl, ends_l gl, ends_f gr, ends_l gr) with the interface
+// coefficients of fine_ghost_finish: gl = (ic0 yf(tx) + yl(tx - 1)) ic2 and gr = (ic1' yl(tx) + yf(tx + 1)) ic2' row by
+// row, hence the same combination of their y-eliminations; no ghost beyond the first / last x-chunk.
+__global__ void __launch_bounds__(256) fine_ghostsum_kernel(FineView v, const double* __restrict__ tsums,
+                                                            double* __restrict__ sums) {
+  const int i = blockIdx.x * 256 + threadIdx.x;      // ((b px) + tx) py + q
+  if (i >= v.nfield * v.px * v.py) return;
+  const int r = i / v.py, tx = r % v.px, b = r / v.px;
+  const double* ic = v.icoef[0] + ((long)b * (v.px + 1) + tx) * 3;
+  const double2* t = reinterpret_cast<const double2*>(tsums) + 2 * (long)i;
+  const double2 tf = t[0], tl = t[1];                // (ends_f, ends_l) of yf and of yl
+  double2 sl = make_double2(0.0, 0.0), sr = sl;
+  if (tx > 0) {
+    const double2 pl = t[1 - 2 * (long)v.py];        // yl of x-chunk tx - 1
+    sl.x = fma(ic[0], tf.x, pl.x) * ic[2];
+    sl.y = fma(ic[0], tf.y, pl.y) * ic[2];
+  }
+  if (tx < v.px - 1) {
+    const double2 nf = t[2 * (long)v.py];            // yf of x-chunk tx + 1
+    sr.x = fma(ic[4], tl.x, nf.x) * ic[5];
+    sr.y = fma(ic[4], tl.y, nf.y) * ic[5];
+  }
+  double2* s = reinterpret_cast<double2*>(sums) + 2 * (long)i;
+  s[0] = sl;
+  s[1] = sr;
 }

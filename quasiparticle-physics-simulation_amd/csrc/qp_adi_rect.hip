@@ -525,8 +525,9 @@ struct qp_adi_rect_plan {
   double* d_fiface0_next = nullptr;
   double* d_fiface1_next = nullptr;
   double* d_fphi = nullptr;      // [nfield][3 x-chunk variants][2][FS] (FineOnePass::phi)
-  double* d_fwy = nullptr;       // [nfield][3 y-chunk variants][2][FS] first / last rows of A_y^-1 (fine_ghostsum_kernel)
+  double* d_fwy = nullptr;       // [nfield][3 y-chunk variants][2][FS] first / last rows of A_y^-1 (FineOnePass::wy)
   double* d_fsums = nullptr;     // [2][nfield][px][py][4] ghost sums S: [0] stays zero (first step), [1] fine_ghostsum_kernel
+  double* d_ftsums = nullptr;    // [nfield][px][py][4] tile sums T (FineOnePass::tsums): F' writes, fine_ghostsum_kernel reads
   double* d_alpha = nullptr;
   double* d_tab = nullptr;
   double* d_ctab = nullptr;
@@ -833,6 +834,7 @@ static void fine_plan_prepare(qp_adi_rect_plan* plan, double r, const double* dc
     slab.upload_owned(std::move(wy), &plan->d_fwy);
     slab.zeros((size_t)nfield * (2 * spec[1].P + 2) * nx, &plan->d_fiface1_next);
     slab.zeros((size_t)2 * nfield * spec[0].P * spec[1].P * 4, &plan->d_fsums);
+    slab.zeros((size_t)nfield * spec[0].P * spec[1].P * 4, &plan->d_ftsums);
   }
   f.bsrc = nullptr;
   f.bscale = 0.0;
@@ -890,9 +892,11 @@ static int fine_steps_fused(qp_adi_rect_plan* plan, double* u, int nsteps, hipSt
 }
 
 // qp_adi_rect_steps on a one-pass plan: ENTRY, R of the first step, then per step one plane pass - F' (fine_onepass_kernel
-// <1>: the fused pass plus P of the next step's y-interface rows) and the small ghost-sum pass X of the next step, and on
-// the last step the exit form of F'.  Step s reads the x-interface rows from ix[s % 2] and the y-interface rows from
-// iy[s % 2] (full rows after R on step 0, with the all-zero sums; P form after that), and writes buffer (s + 1) % 2 of both.
+// <1>: the fused pass plus P of the next step's y-interface rows and the tile sums T of the x-interface rows it writes)
+// and the ghost-sum pass X of the next step (T -> S, one thread per chunk pair), and on the last step the exit form of F'.
+// The entry pass leaves no T: step 0 takes the all-zero sums, and every later step's S comes from the F' before it.
+// Step s reads the x-interface rows from ix[s % 2] and the y-interface rows from iy[s % 2] (full rows after R on step 0,
+// with the all-zero sums; P form after that), and writes buffer (s + 1) % 2 of both.
 static int fine_steps_onepass(qp_adi_rect_plan* plan, double* u, int nsteps, hipStream_t stream) {
   FineView f = plan->fview;
   const unsigned tiles = (unsigned)((long)f.nfield * (f.ny / 64) * f.px);
@@ -900,7 +904,8 @@ static int fine_steps_onepass(qp_adi_rect_plan* plan, double* u, int nsteps, hip
   double* const ix[2] = {plan->d_fiface[0], plan->d_fiface0_next};
   double* const iy[2] = {plan->d_fiface[1], plan->d_fiface1_next};
   double* const sums = plan->d_fsums + (size_t)f.nfield * f.px * f.py * 4;
-  FineOnePass op{plan->d_fphi, nullptr, nullptr};
+  FineOnePass op{plan->d_fphi, nullptr, nullptr, plan->d_fwy, plan->d_ftsums};
+  const unsigned nsum = (unsigned)(((long)f.nfield * f.px * f.py + 255) / 256);
   f.iface[0] = ix[0];
   f.iface[1] = iy[0];
   QP_LAUNCH_FINE(f.stream, fine_y_kernel, 0, dim3(tiles), dim3(64), 0, stream, f, (const double*)u, w);
@@ -915,9 +920,7 @@ static int fine_steps_onepass(qp_adi_rect_plan* plan, double* u, int nsteps, hip
     op.sums = s == 0 ? plan->d_fsums : sums;
     if (s + 1 < nsteps) {
       QP_LAUNCH_FINE(f.stream, fine_onepass_kernel, 1, dim3(tiles), dim3(64), 0, stream, f, next, w, w, op);
-      FineView fx = f;
-      fx.iface[0] = next;
-      hipLaunchKernelGGL(fine_ghostsum_kernel, dim3(tiles), dim3(64), 0, stream, fx, (const double*)plan->d_fwy, sums);
+      hipLaunchKernelGGL(fine_ghostsum_kernel, dim3(nsum), dim3(256), 0, stream, f, (const double*)plan->d_ftsums, sums);
     } else {
       QP_LAUNCH_FINE(f.stream, fine_onepass_kernel, 2, dim3(tiles), dim3(64), 0, stream, f, next, w, u, op);
     }
