@@ -81,7 +81,7 @@ __device__ __forceinline__ void explicit32(double (&e)[FS], double gl, double gr
 }
 
 // First / last entry of A_p^-1 e (the reduced right-hand sides of the chunk).  The fine tables carry the two eliminations
-// in scaled form (fine_plan_create): d~_k = dp_k / ew_k obeys d~_k = eawf'_k d~_{k-1} + e_k, one FMA per cell, and
+// in scaled form (fine_plan_prepare): d~_k = dp_k / ew_k obeys d~_k = eawf'_k d~_{k-1} + e_k, one FMA per cell, and
 // yl = ew_last d~_last; likewise backwards with yf = ev_0 b~_0.
 template <class Coef>
 __device__ __forceinline__ void ends32(const double (&e)[FS], const Coef& t, double& yf, double& yl) {
@@ -143,16 +143,12 @@ __device__ __forceinline__ void transpose32h(double (&v)[FS], double* lds, int l
   }
 }
 
-struct FineGhost {
-  double q0, q1, q2, q3;
-};
-
 // reduced right-hand sides next to chunk p of `line` (always in bounds: rows 0 and 2P+1 exist and hold zeros)
-__device__ __forceinline__ FineGhost fine_ghost_prefetch(const FineView& v, int dir, int b, int p, long line) {
+__device__ __forceinline__ GhostRaw fine_ghost_prefetch(const FineView& v, int dir, int b, int p, long line) {
   const int P = dir == 0 ? v.px : v.py;
   const long nlines = dir == 0 ? v.ny : v.nx;
   const double* ir = v.iface[dir] + (long)b * (2 * P + 2) * nlines + line;
-  FineGhost g;
+  GhostRaw g;
   if (QP_ABL & 1) { g.q0 = g.q1 = g.q2 = g.q3 = 0.0; return g; }
   g.q0 = ir[(long)(2 * p) * nlines];
   g.q1 = ir[(long)(2 * p + 1) * nlines];
@@ -162,7 +158,7 @@ __device__ __forceinline__ FineGhost fine_ghost_prefetch(const FineView& v, int 
 }
 
 // the two 2 x 2 interface systems of chunk p (see ghost_finish): gl = E_{p-1}, gr = F_{p+1}
-__device__ __forceinline__ void fine_ghost_finish(const FineView& v, int dir, int b, int p, const FineGhost& g, double& gl,
+__device__ __forceinline__ void fine_ghost_finish(const FineView& v, int dir, int b, int p, const GhostRaw& g, double& gl,
                                                   double& gr) {
   const int P = dir == 0 ? v.px : v.py;
   const ctab_t ic = as_const(v.icoef[dir] + (long)b * (P + 1) * 3);
@@ -264,7 +260,7 @@ __device__ __forceinline__ void fine_x_front(const FineView& v, const FineXTile&
   const long ncell = (long)v.ny * v.nx;
   const double a = as_const(v.alpha)[b];
   const int row = ty * 64 + lane;      // lane = row between the transposes
-  const FineGhost graw = fine_ghost_prefetch(v, 0, b, tx, row);
+  const GhostRaw graw = fine_ghost_prefetch(v, 0, b, tx, row);
   const CoefFine cx = parts[0];
   fine_load_rows<STREAM>(tile + off, v.nx, e);
   warm_scalar_cache(parts);
@@ -388,7 +384,7 @@ __device__ __forceinline__ void fine_y_body(const FineView& v, const FineView& v
   const double a = as_const(v.alpha)[b];
   const int col = tx * 64 + lane;
   const int j0 = ty * FS;
-  FineGhost graw;
+  GhostRaw graw;
   if (MODE == 1 || MODE == 2) graw = fine_ghost_prefetch(v, 1, b, ty, col);
   const CoefFine cy = fine_coefs(v, 1, b, chunk_variant(ty, v.py), 0);
   const CoefFine cyn = NEXT ? fine_coefs(vn, 1, b, chunk_variant(ty, v.py), 0) : cy;
@@ -460,7 +456,7 @@ struct CoefFinePair {       // chunk p_even on lanes 0..31, chunk p_even + 1 on 
 
 // fine_ghost_finish for chunk p_even + h on half-wave h (same coefficients, same operations, per-lane selects)
 __device__ __forceinline__ void fine_ghost_finish_pair(const FineView& v, int dir, int b, int p_even, int h,
-                                                       const FineGhost& g, double& gl, double& gr) {
+                                                       const GhostRaw& g, double& gl, double& gr) {
   const int P = dir == 0 ? v.px : v.py;
   const ctab_t ic = as_const(v.icoef[dir] + (long)b * (P + 1) * 3);
   const int p = p_even + h;
@@ -513,7 +509,7 @@ __device__ __forceinline__ FineGhostSums fine_ghost_sums_prefetch(const FineView
 }
 
 // q0..q3 in P form -> the y-reduced right-hand sides (rows 0 and 2 py + 1 hold zeros and keep them)
-__device__ __forceinline__ void fine_ghost_correct(const FineView& v, int yc, const FineGhostSums& r, FineGhost& g) {
+__device__ __forceinline__ void fine_ghost_correct(const FineView& v, int yc, const FineGhostSums& r, GhostRaw& g) {
   if (yc > 0) g.q0 = fma(r.fl, r.s[0], fma(r.fr, r.s[1], g.q0));
   g.q1 = fma(r.fl, r.s[2], fma(r.fr, r.s[4], g.q1));
   g.q2 = fma(r.fl, r.s[3], fma(r.fr, r.s[5], g.q2));
@@ -554,7 +550,7 @@ __device__ __forceinline__ void fine_fused_body(const FineView& v, double* iface
   const int col = tx * FS + c;
   const int yc = 2 * ty + h;           // the y-chunk of this lane after fine_x_front
   const int va = chunk_variant(2 * ty, v.py), vb = chunk_variant(2 * ty + 1, v.py);
-  FineGhost gyraw = fine_ghost_prefetch(v, 1, b, yc, col);
+  GhostRaw gyraw = fine_ghost_prefetch(v, 1, b, yc, col);
   FineGhostSums gs{};
   if (ONEPASS) gs = fine_ghost_sums_prefetch(v, op, b, tx, yc, c);
   CoefFine parts[4];

@@ -31,6 +31,7 @@
 // a source-plane argument.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "qp_tile_common.h"
@@ -350,7 +351,7 @@ static void solve_chunk(const std::vector<double>& bdiag, double a, std::vector<
 }
 
 // table of chunk p of a line cut into chunks of L cells (L = TS for the 64 x 64 tiles, FS for the fine tiles): [T_NSLOT][L]
-void build_chunk_table_len(const DirSpec& s, double a, int p, int L, double* tab, double ends[4]) {
+void build_chunk_table(const DirSpec& s, double a, int p, int L, double* tab, double ends[4]) {
   const int len = std::min(L, s.n - p * L);
   std::vector<double> bd;
   chunk_diagonal(s, a, p, L, len, bd);
@@ -401,10 +402,6 @@ void build_chunk_table_len(const DirSpec& s, double a, int p, int L, double* tab
   ends[3] = h[len - 1];
 }
 
-void build_chunk_table(const DirSpec& s, double a, int p, double* tab, double ends[4]) {
-  build_chunk_table_len(s, a, p, TS, tab, ends);
-}
-
 // Reduced-system data of one (field, direction).  `s` describes the GLOBAL line; the local block holds chunks
 // [p0, p0 + Ploc).  Fills icoef[Ploc+1][3] (interface q sits between local chunks q-1 and q; q = 0 / Ploc touch the
 // neighbouring blocks) and, when `lu` is non-NULL (no decomposition: p0 == 0, Ploc == s.P), the banded LU factors
@@ -416,7 +413,7 @@ static double reduced_tables(const DirSpec& s, double a, int p0, int Ploc, doubl
   double far = 0.0;
   for (int p = 0; p < s.P; ++p) {
     double ends[4];
-    build_chunk_table_len(s, a, p, L, tab.data(), ends);
+    build_chunk_table(s, a, p, L, tab.data(), ends);
     near_g[p] = a * ends[0];   // weight of E_{p-1} in the F_p equation
     far_g[p] = a * ends[1];    // weight of E_{p-1} in the E_p equation
     far_h[p] = a * ends[2];    // weight of F_{p+1} in the F_p equation
@@ -467,76 +464,169 @@ static double reduced_tables(const DirSpec& s, double a, int p0, int Ploc, doubl
 
 #include "qp_adi_fine.inc"
 
+// ---------------------------------------------------------------------------------------------------------
+// host side: launches
+// ---------------------------------------------------------------------------------------------------------
+// Run-time choices of a plan become template arguments here and nowhere else: f receives std::integral_constant values.
+template <class F>
+static void with_bool(bool on, F f) {
+  if (on) f(std::true_type());
+  else f(std::false_type());
+}
+
+// the plan's stream mode: 0 cached, 2 non-temporal stores, 3 non-temporal both (1 is served by the kernels of 3)
+template <class F>
+static void with_stream(int mode, F f) {
+  if (mode == 0) f(std::integral_constant<int, 0>());
+  else if (mode == 2) f(std::integral_constant<int, 2>());
+  else f(std::integral_constant<int, 3>());
+}
+
+// ... and, for the 64 x 64 kernels, its table form (compact: constant middle of every slot; otherwise every entry is fetched)
+template <class F>
+static void with_stream_compact(const RectView& v, F f) {
+  with_stream(v.d.stream, [&](auto S) { with_bool(v.compact != 0, [&](auto C) { f(S, C); }); });
+}
+
+// One launch function per pass, one wave per tile.  launch_y / launch_x / launch_reduced exist for both views, so that a
+// sequence of passes is written once for the two tile families.  Fine tiles: nfield * (ny / 64) * px = nfield * py * (nx / 64).
+static dim3 tile_grid(const FineView& f) { return dim3((unsigned)((long)f.nfield * (f.ny / 64) * f.px)); }
+static dim3 tile_grid(const RectView& v) { return dim3((unsigned)((long)v.d.nfield * v.d.py * v.d.px)); }
+
+template <int MODE, bool SRC = false>      // MODE 0 entry, 1 carry, 2 exit, 3 reduce
+static void launch_y(const FineView& f, const double* src, double* dst, hipStream_t st) {
+  with_stream(f.stream, [&](auto S) {
+    hipLaunchKernelGGL((fine_y_kernel<MODE, decltype(S)::value, SRC>), tile_grid(f), dim3(64), 0, st, f, src, dst);
+  });
+}
+template <int MODE, bool SRC = false>
+static void launch_y(const RectView& v, const double* src, double* dst, hipStream_t st) {
+  with_stream_compact(v, [&](auto S, auto C) {
+    hipLaunchKernelGGL((rect_y_kernel<MODE, decltype(S)::value, decltype(C)::value, SRC>), tile_grid(v), dim3(64), 0, st, v,
+                       src, dst);
+  });
+}
+
+template <bool EXPLICIT, bool SRC = false>
+static void launch_x(const FineView& f, double* buf, hipStream_t st) {
+  with_stream(f.stream, [&](auto S) {
+    hipLaunchKernelGGL((fine_x_kernel<EXPLICIT, decltype(S)::value, SRC>), tile_grid(f), dim3(64), 0, st, f, buf);
+  });
+}
+template <bool EXPLICIT, bool SRC = false>
+static void launch_x(const RectView& v, double* buf, hipStream_t st) {
+  with_stream_compact(v, [&](auto S, auto C) {
+    hipLaunchKernelGGL((rect_x_kernel<EXPLICIT, decltype(S)::value, decltype(C)::value, SRC>), tile_grid(v), dim3(64), 0, st,
+                       v, buf);
+  });
+}
+
+// banded reduced systems of direction `dir`; nothing to run where the interfaces decouple - on fine tiles always
+static void launch_reduced(const FineView&, int, hipStream_t) {}
+static void launch_reduced(const RectView& v, int dir, hipStream_t st) {
+  if (v.decoupled[dir]) return;
+  const long lines = (long)(dir == 0 ? v.d.ny : v.d.nx) * v.d.nfield;
+  hipLaunchKernelGGL(rect_reduced_kernel, dim3((unsigned)((lines + 63) / 64)), dim3(64), 0, st, v, dir);
+}
+
+static void launch_fine_reduce(const FineView& f, const double* buf, hipStream_t st) {
+  with_stream(f.stream, [&](auto S) {
+    hipLaunchKernelGGL((fine_reduce_kernel<decltype(S)::value>), tile_grid(f), dim3(64), 0, st, f, buf);
+  });
+}
+
+template <int MODE>      // 1 carry (dst == w), 2 exit
+static void launch_fine_fused(const FineView& f, double* iface0_next, double* w, double* dst, hipStream_t st) {
+  with_stream(f.stream, [&](auto S) {
+    hipLaunchKernelGGL((fine_fused_kernel<MODE, decltype(S)::value>), tile_grid(f), dim3(64), 0, st, f, iface0_next, w, dst);
+  });
+}
+
+template <int MODE>
+static void launch_fine_onepass(const FineView& f, double* iface0_next, double* w, double* dst, const FineOnePass& op,
+                                hipStream_t st) {
+  with_stream(f.stream, [&](auto S) {
+    hipLaunchKernelGGL((fine_onepass_kernel<MODE, decltype(S)::value>), tile_grid(f), dim3(64), 0, st, f, iface0_next, w, dst,
+                       op);
+  });
+}
+
+static void launch_fine_ghostsum(const FineView& f, const double* tsums, double* sums, hipStream_t st) {
+  const unsigned blocks = (unsigned)(((long)f.nfield * f.px * f.py + 255) / 256);
+  hipLaunchKernelGGL(fine_ghostsum_kernel, dim3(blocks), dim3(256), 0, st, f, tsums, sums);
+}
+
+static void launch_fine_y_next(const FineView& f, const FineView& fn, double* w, hipStream_t st) {
+  with_stream(f.stream, [&](auto S) {
+    hipLaunchKernelGGL((fine_y_next_kernel<decltype(S)::value>), tile_grid(f), dim3(64), 0, st, f, fn, w);
+  });
+}
+
+// a view whose passes add scale * b to every right-hand side they form (Peaceman-Rachford iterations: kernels <..., SRC = true>)
+template <class View>
+static View with_source(View v, const double* b, double scale) {
+  v.bsrc = b;
+  v.bscale = scale;
+  return v;
+}
+
+// The three passes of a Peaceman-Rachford iteration (<0, true, true>: u -> w -> u) and of the ADI preconditioner
+// (<3, false, false>: in place): y-pass FIRST from src into w, x-pass on w, exit y-pass from w into dst, with the reduced
+// systems of the 64 x 64 tiles in between.
+template <int FIRST, bool EXPLICIT, bool SRC, class View>
+static void three_passes(const View& v, const double* src, double* w, double* dst, hipStream_t st) {
+  launch_y<FIRST, SRC>(v, src, w, st);
+  launch_reduced(v, 0, st);
+  launch_x<EXPLICIT, SRC>(v, w, st);
+  launch_reduced(v, 1, st);
+  launch_y<2>(v, w, dst, st);
+}
+
+// the passes of qp_adi_rect_phase (u may be NULL where the phase does not touch it)
+template <class View>
+static bool run_phase(const View& v, int phase, double* u, double* w, hipStream_t st) {
+  switch (phase) {
+    case QP_ADI_ENTRY: launch_y<0>(v, u, w, st); return true;
+    case QP_ADI_REDUCED_X: launch_reduced(v, 0, st); return true;
+    case QP_ADI_SWEEP_X: launch_x<true>(v, w, st); return true;
+    case QP_ADI_REDUCED_Y: launch_reduced(v, 1, st); return true;
+    case QP_ADI_SWEEP_Y_CARRY: launch_y<1>(v, w, w, st); return true;
+    case QP_ADI_SWEEP_Y_EXIT: launch_y<2>(v, w, u, st); return true;
+    default: return false;
+  }
+}
+
+// How qp_adi_rect_steps runs on a plan; fixed at plan creation (rect_plan_create_impl).
+enum StepForm {
+  STEPS_TILES64 = 0,     // 64 x 64 tiles, two sweeps per step
+  STEPS_FINE,            // fine tiles (qp_adi_fine.inc), two sweeps per step: every pass of the plan runs the 32-cell-chunk kernels
+  STEPS_FUSED,           // fine tiles, reduce pass + fused pass per step (fine_steps_fused)
+  STEPS_ONEPASS,         // fine tiles, one-pass steps (fine_steps_onepass)
+};
+
+// Fine-tile state of a plan.  What is valid follows from `form` alone: nothing at STEPS_TILES64; `view` from STEPS_FINE on (its
+// own interface arrays; the 64 x 64 view stays valid for qp_adi_rect_combine and the plan queries); `ix_next` from
+// STEPS_FUSED on; the rest at STEPS_ONEPASS.  Everything else stays null.
+struct FineState {
+  int form = STEPS_TILES64;
+  FineView view{};
+  // fused steps: the x-interface rows ping-pong between view.iface[0] and ix_next (the fused pass writes the rows its
+  // neighbours are still reading)
+  double* ix_next = nullptr;
+  // one-pass steps: phi, wy and tsums of `op` are the plan's (sums and p_next change per step); the y-interface rows in P
+  // form ping-pong between view.iface[1] and iy_next
+  FineOnePass op{};
+  double* iy_next = nullptr;
+  double* sums[2] = {nullptr, nullptr};   // ghost sums S, [nfield][px][py][4] each: [0] stays zero (first step), [1] fine_ghostsum_kernel
+  bool on() const { return form != STEPS_TILES64; }
+};
+
 }  // namespace qp
-
-// launches NAME<ARG, STREAM> for the plan's stream mode (0 cached, 2 non-temporal stores, 3 non-temporal both)
-#define QP_LAUNCH_STREAMED_C(mode, NAME, ARG, C, ...)                              \
-  do {                                                                             \
-    if ((mode) == 0) hipLaunchKernelGGL((NAME<ARG, 0, C>), __VA_ARGS__);           \
-    else if ((mode) == 2) hipLaunchKernelGGL((NAME<ARG, 2, C>), __VA_ARGS__);      \
-    else hipLaunchKernelGGL((NAME<ARG, 3, C>), __VA_ARGS__);                       \
-  } while (0)
-#define QP_LAUNCH_STREAMED_SRC(mode, compact, NAME, ARG, ...)                                              \
-  do {                                                                                                   \
-    if (compact) {                                                                                       \
-      if ((mode) == 0) hipLaunchKernelGGL((NAME<ARG, 0, true, true>), __VA_ARGS__);                      \
-      else if ((mode) == 2) hipLaunchKernelGGL((NAME<ARG, 2, true, true>), __VA_ARGS__);                 \
-      else hipLaunchKernelGGL((NAME<ARG, 3, true, true>), __VA_ARGS__);                                  \
-    } else {                                                                                             \
-      if ((mode) == 0) hipLaunchKernelGGL((NAME<ARG, 0, false, true>), __VA_ARGS__);                     \
-      else if ((mode) == 2) hipLaunchKernelGGL((NAME<ARG, 2, false, true>), __VA_ARGS__);                \
-      else hipLaunchKernelGGL((NAME<ARG, 3, false, true>), __VA_ARGS__);                                 \
-    }                                                                                                    \
-  } while (0)
-// ... and for the plan's table form (compact: constant middle of every slot; otherwise every entry is fetched)
-#define QP_LAUNCH_STREAMED(mode, compact, NAME, ARG, ...)                          \
-  do {                                                                             \
-    if (compact) QP_LAUNCH_STREAMED_C(mode, NAME, ARG, true, __VA_ARGS__);         \
-    else QP_LAUNCH_STREAMED_C(mode, NAME, ARG, false, __VA_ARGS__);                \
-  } while (0)
-
-#define QP_LAUNCH_FINE(mode, NAME, ARG, ...)                                       \
-  do {                                                                             \
-    if ((mode) == 0) hipLaunchKernelGGL((NAME<ARG, 0>), __VA_ARGS__);              \
-    else if ((mode) == 2) hipLaunchKernelGGL((NAME<ARG, 2>), __VA_ARGS__);         \
-    else hipLaunchKernelGGL((NAME<ARG, 3>), __VA_ARGS__);                          \
-  } while (0)
-
-#define QP_LAUNCH_FINE_SRC(mode, NAME, ARG, ...)                                \
-  do {                                                                             \
-    if ((mode) == 0) hipLaunchKernelGGL((NAME<ARG, 0, true>), __VA_ARGS__);        \
-    else if ((mode) == 2) hipLaunchKernelGGL((NAME<ARG, 2, true>), __VA_ARGS__);   \
-    else hipLaunchKernelGGL((NAME<ARG, 3, true>), __VA_ARGS__);                    \
-  } while (0)
 
 struct qp_adi_rect_plan {
   qp::RectView view;
-  // fine tiles (qp_adi_fine.inc): when `fine`, every pass of this plan runs the 32-cell-chunk kernels on their own
-  // interface arrays (the 64 x 64 view above stays valid for qp_adi_rect_combine and the plan queries)
-  bool fine = false;
-  qp::FineView fview;
-  double* d_fctab = nullptr;
-  double* d_ficoef[2] = {nullptr, nullptr};
-  double* d_fiface[2] = {nullptr, nullptr};
-  // fused steps (qp_adi_rect_steps): 1 = reduce pass + fused pass per step, 2 = one-pass steps (fine_steps_onepass); the
-  // x-interface rows ping-pong between d_fiface[0] and d_fiface0_next (the fused pass writes the rows its neighbours are
-  // still reading), and on one-pass plans the y-interface rows in P form between d_fiface[1] and d_fiface1_next
-  int fused = 0;
-  double* d_fiface0_next = nullptr;
-  double* d_fiface1_next = nullptr;
-  double* d_fphi = nullptr;      // [nfield][3 x-chunk variants][2][FS] (FineOnePass::phi)
-  double* d_fwy = nullptr;       // [nfield][3 y-chunk variants][2][FS] first / last rows of A_y^-1 (FineOnePass::wy)
-  double* d_fsums = nullptr;     // [2][nfield][px][py][4] ghost sums S: [0] stays zero (first step), [1] fine_ghostsum_kernel
-  double* d_ftsums = nullptr;    // [nfield][px][py][4] tile sums T (FineOnePass::tsums): F' writes, fine_ghostsum_kernel reads
-  double* d_alpha = nullptr;
-  double* d_tab = nullptr;
-  double* d_ctab = nullptr;
-  double* d_lu[2] = {nullptr, nullptr};
-  double* d_icoef[2] = {nullptr, nullptr};
-  double* d_iface[2] = {nullptr, nullptr};
-  double* d_z[2] = {nullptr, nullptr};
-  double* d_uhalo[2] = {nullptr, nullptr};
-  double* d_slab = nullptr;  // ONE device allocation behind every table / interface pointer above and below (SlabBuilder)
+  qp::FineState fine;
+  double* d_slab = nullptr;  // ONE device allocation behind every table / interface pointer of the two views (SlabBuilder)
   double* d_work = nullptr;  // [nfield][ncell] carried right-hand side
   bool owns_work = true;     // false: d_work belongs to another plan (qp_adi_rect_plan_create_pr with `share`)
   double pr_scale = 0.0;     // != 0: Peaceman-Rachford iteration plan, 1 / (1/2 + p)
@@ -655,11 +745,10 @@ __global__ void __launch_bounds__(256) rect_combine_kernel(int ny, int nx, int n
   }
 }
 
-// Fine tiles are eligible on undecomposed grids whose extents are multiples of 64.  QPSIM_FINE_TILES=0 / 1 forces the
-// choice (1: whenever the plan qualifies); the default is the size rule measured on MI355X.
 // All small device arrays of a plan live in one allocation: a plan used to cost ~17 hipMalloc + as many blocking copies
 // (~3 ms), which showed when the host builds a Peaceman-Rachford cycle of 7-8 plans for a 200-step run on a 64^2 grid.
 // Uploads are staged in one host buffer and copied once; the zero-filled arrays follow and get one hipMemset.
+// `dst` is the view member the array is bound to at commit - its only home (mut() for the const double* members).
 struct SlabBuilder {
   struct Item {
     double** dst;
@@ -669,6 +758,7 @@ struct SlabBuilder {
   std::vector<Item> items;
   std::vector<std::vector<double>> owned;      // host arrays whose builders have returned
   static size_t pad(size_t n) { return (n + 31) & ~(size_t)31; }      // 256-byte granules
+  static double** mut(const double** p) { return const_cast<double**>(p); }
   void upload(const std::vector<double>& h, double** dst) { items.push_back({dst, h.size(), h.data()}); }
   void upload_owned(std::vector<double>&& h, double** dst) {
     owned.push_back(std::move(h));
@@ -699,26 +789,42 @@ struct SlabBuilder {
   }
 };
 
-static bool fine_tiles_allowed() {      // QPSIM_FINE_TILES=0 switches the fine kernels off everywhere
-  const char* e = getenv("QPSIM_FINE_TILES");
-  return !e || atoi(e) != 0;
+// representative global chunk of a table variant on a line of P chunks: 0 interior -> 1, 1 first -> 0, 2 last -> P - 1,
+// 3 single -> 0; -1 where the line has no such chunk
+static int variant_chunk(int var, int P) {
+  switch (var) {
+    case 0: return P >= 3 ? 1 : -1;
+    case 1: return P >= 2 ? 0 : -1;
+    case 2: return P >= 2 ? P - 1 : -1;
+    default: return P == 1 ? 0 : -1;
+  }
 }
 
-// Fused ADI steps on fine plans: 0 two sweeps, 1 reduce + fused pass (24 instead of 32 B of plane traffic
-// per cell-update), 2 one-pass steps (16 B after the first step).  QPSIM_ADI_FUSED=0 / 1 / 2 forces the choice (1 and 2: on
-// every fine plan; any other non-zero value means 1).  The default is the size rule measured on MI355X (ms per step, two
-// sweeps / reduce + fused): 4096^2 0.094 / 0.080, 1024^2 x 12 0.232 / 0.225 (c2), 2048^2 0.0262 / 0.0259 - but 1024^2
-// 0.0125 / 0.0135: below 4 Mi cells the fused pass's longer serial stretch per tile is exposed (2 tiles per SIMD) and the
-// bytes saved are cheap.  Where fused steps run, the one-pass form replaces them (see DESIGN.md for its A/B).
+// Fine tiles are eligible on undecomposed grids whose extents are multiples of 64 (rect_plan_create_impl).
+// QPSIM_FINE_TILES=0 / 1 forces the choice (0: off everywhere; 1: whenever the plan qualifies).  The default: always for the
+// plans of a Peaceman-Rachford iteration (`pr`), the size rule measured on MI355X for step plans.
+static bool fine_tiles_wanted(bool pr, int nfield, int ny, int nx) {
+  if (const char* e = getenv("QPSIM_FINE_TILES")) return atoi(e) != 0;
+  // sweep time in us, 64 x 64 tiles / fine tiles: 1024^2 7.55 / 5.91, 2048^2 15.1 / 13.2, 512^2 x 12 11.8 / 10.2,
+  // 4160 x 2176 28.7 / 25.8, 4096^2 47.0 / 45.9; beyond the cached regime 5760^2 86.9 / 92.7, 8192^2 189 / 187
+  return pr || stream_mode((size_t)nfield * ny * nx * sizeof(double)) == 0;
+}
+
+// Step form of a fine plan: STEPS_FINE two sweeps, STEPS_FUSED reduce + fused pass (24 instead of 32 B of plane
+// traffic per cell-update), STEPS_ONEPASS one-pass steps (16 B after the first step).  QPSIM_ADI_FUSED=0 / 1 / 2 forces the
+// choice (1 and 2: on every fine plan; any other non-zero value means 1).  The default is the size rule measured on MI355X
+// (ms per step, two sweeps / reduce + fused): 4096^2 0.094 / 0.080, 1024^2 x 12 0.232 / 0.225 (c2), 2048^2 0.0262 / 0.0259 -
+// but 1024^2 0.0125 / 0.0135: below 4 Mi cells the fused pass's longer serial stretch per tile is exposed (2 tiles per SIMD)
+// and the bytes saved are cheap.  Where fused steps run, the one-pass form replaces them (see DESIGN.md for its A/B).
 // Only plain step plans: Peaceman-Rachford plans never run steps.
-static int fine_fused_wanted(const qp_adi_rect_plan* plan) {
-  if (plan->pr_scale != 0.0) return 0;
+static int fine_step_form(const qp_adi_rect_plan* plan) {
+  if (plan->pr_scale != 0.0) return STEPS_FINE;
   if (const char* e = getenv("QPSIM_ADI_FUSED")) {
     const int m = atoi(e);
-    return m == 0 ? 0 : m == 2 ? 2 : 1;
+    return m == 0 ? STEPS_FINE : m == 2 ? STEPS_ONEPASS : STEPS_FUSED;
   }
-  const FineView& f = plan->fview;
-  return (long)f.nfield * f.ny * f.nx >= 4L * 1024 * 1024 ? 2 : 0;
+  const RectDims& d = plan->view.d;
+  return (long)d.nfield * d.ny * d.nx >= 4L * 1024 * 1024 ? STEPS_ONEPASS : STEPS_FINE;
 }
 
 // One-pass tables of a chunk (fine_plan_prepare, from the table entries the kernels read):
@@ -755,50 +861,34 @@ static void fine_end_rows(const double* tab, double* w) {       // w[2][FS]
   for (int k = FS - 2; k >= 0; --k) w[FS + k] = w[FS + k + 1] * tab[T_EAWF * FS + k + 1];
 }
 
-static bool fine_tiles_wanted(int nfield, int ny, int nx) {
-  if (ny % 64 != 0 || nx % 64 != 0) return false;
-  if (const char* e = getenv("QPSIM_FINE_TILES")) return atoi(e) != 0;
-  // sweep time in us, 64 x 64 tiles / fine tiles: 1024^2 7.55 / 5.91, 2048^2 15.1 / 13.2, 512^2 x 12 11.8 / 10.2,
-  // 4160 x 2176 28.7 / 25.8, 4096^2 47.0 / 45.9; beyond the cached regime 5760^2 86.9 / 92.7, 8192^2 189 / 187
-  return stream_mode((size_t)nfield * ny * nx * sizeof(double)) == 0;
-}
-
-// Tables, interface coefficients and interface arrays of the fine view; leaves plan->fine false (and no error) when the
-// plan does not qualify: chunks of 32 cells not decoupled at this r D, or a table without the compact form.
-static void fine_plan_prepare(qp_adi_rect_plan* plan, double r, const double* dcoef_host, const DirSpec (&coarse)[2],
-                              SlabBuilder& slab) {
+// Tables, interface coefficients and interface arrays of the fine tiles for step form `form`, bound into plan->fine.
+// Returns false, with nothing queued or bound, when the plan does not qualify: chunks of 32 cells not decoupled at this
+// r D, or a table without the compact form.  alpha[b] = r D_b (the caller's upload, alive until the commit).
+static bool fine_plan_prepare(qp_adi_rect_plan* plan, int form, const std::vector<double>& alpha,
+                              const DirSpec (&coarse)[2], SlabBuilder& slab) {
   const RectView& v = plan->view;
   const int nfield = v.d.nfield, ny = v.d.ny, nx = v.d.nx;
-  FineView& f = plan->fview;
-  f.ny = ny; f.nx = nx; f.nfield = nfield;
-  f.py = ny / FS; f.px = nx / FS;
-  f.stream = v.d.stream;
-  for (int d = 0; d < 2; ++d)
-    for (int k = 0; k < 2; ++k) f.other_src[d][k] = v.other_src[d][k];
   DirSpec spec[2] = {coarse[0], coarse[1]};
-  spec[0].P = f.px;
-  spec[1].P = f.py;
+  spec[0].P = nx / FS;
+  spec[1].P = ny / FS;
   std::vector<double> tab((size_t)T_NSLOT * FS);
   std::vector<double> ctab((size_t)2 * nfield * 4 * 2 * CT_PART, 0.0);
   std::vector<double> icoef[2];
   for (int d = 0; d < 2; ++d) icoef[d].assign((size_t)nfield * (spec[d].P + 1) * 3, 0.0);
-  const int fused = fine_fused_wanted(plan);
   std::vector<double> phi, wy;            // one-pass tables per (field, variant): x-ghost responses, A_y^-1 end rows
-  if (fused == 2) {
+  if (form == STEPS_ONEPASS) {
     phi.assign((size_t)nfield * 3 * 2 * FS, 0.0);
     wy.assign((size_t)nfield * 3 * 2 * FS, 0.0);
   }
   for (int b = 0; b < nfield; ++b) {
-    const double a = r * dcoef_host[b];
+    const double a = alpha[b];
     for (int d = 0; d < 2; ++d) {
-      const int P = spec[d].P;       // >= 2
+      const int P = spec[d].P;       // >= 2: no single-chunk variant
       for (int var = 0; var < 3; ++var) {
-        int p;
-        if (var == 0) { if (P < 3) continue; p = 1; }
-        else if (var == 1) p = 0;
-        else p = P - 1;
+        const int p = variant_chunk(var, P);
+        if (p < 0) continue;
         double ends[4];
-        build_chunk_table_len(spec[d], a, p, FS, tab.data(), ends);
+        build_chunk_table(spec[d], a, p, FS, tab.data(), ends);
         {
           // scaled eliminations (ends32): eawf'_k = eawf_k ew_{k-1} / ew_k, eav'_k = eav_k ev_{k+1} / ev_k; of EW / EV only
           // the last / first entry is read.  (Full chunks: no padded entries, every pivot is positive.)
@@ -809,84 +899,68 @@ static void fine_plan_prepare(qp_adi_rect_plan* plan, double r, const double* dc
           for (int k = 0; k < FS - 1; ++k) eav[k] = eav[k] * ev[k + 1] / ev[k];
           eav[FS - 1] = 0.0;
         }
-        if (!table_is_compact_len(FS, tab.data())) return;
-        build_compact_table_len(FS, tab.data(), &ctab[(((size_t)d * nfield + b) * 4 + var) * 2 * CT_PART]);
-        if (fused == 2) {
+        if (!table_is_compact(FS, tab.data())) return false;
+        build_compact_table(FS, tab.data(), &ctab[(((size_t)d * nfield + b) * 4 + var) * 2 * CT_PART]);
+        if (form == STEPS_ONEPASS) {
           const size_t o = ((size_t)b * 3 + var) * 2 * FS;
           if (d == 0) fine_ghost_response(tab.data(), a, &phi[o]);
           else fine_end_rows(tab.data(), &wy[o]);
         }
       }
       const double far = reduced_tables(spec[d], a, 0, P, nullptr, &icoef[d][(size_t)b * (P + 1) * 3], FS);
-      if (!(far < kFarCouplingDrop)) return;
+      if (!(far < kFarCouplingDrop)) return false;
     }
   }
-  slab.upload_owned(std::move(ctab), &plan->d_fctab);
+  FineState& fs = plan->fine;
+  FineView& f = fs.view;
+  f.ny = ny; f.nx = nx; f.nfield = nfield;
+  f.py = spec[1].P; f.px = spec[0].P;
+  f.stream = v.d.stream;
+  for (int d = 0; d < 2; ++d)
+    for (int k = 0; k < 2; ++k) f.other_src[d][k] = v.other_src[d][k];
+  const size_t xrows = (size_t)nfield * (2 * f.px + 2) * ny, yrows = (size_t)nfield * (2 * f.py + 2) * nx;
+  const size_t nsums = (size_t)nfield * f.px * f.py * 4;
+  slab.upload(alpha, slab.mut(&f.alpha));
+  slab.upload_owned(std::move(ctab), slab.mut(&f.ctab));
   for (int d = 0; d < 2; ++d) {
-    const size_t nlines = d == 0 ? ny : nx;
-    slab.upload_owned(std::move(icoef[d]), &plan->d_ficoef[d]);
-    slab.zeros((size_t)nfield * (2 * spec[d].P + 2) * nlines, &plan->d_fiface[d]);
+    slab.upload_owned(std::move(icoef[d]), slab.mut(&f.icoef[d]));
+    slab.zeros(d == 0 ? xrows : yrows, &f.iface[d]);
   }
-  plan->fused = fused;
-  if (fused) slab.zeros((size_t)nfield * (2 * spec[0].P + 2) * ny, &plan->d_fiface0_next);
-  if (fused == 2) {
-    slab.upload_owned(std::move(phi), &plan->d_fphi);
-    slab.upload_owned(std::move(wy), &plan->d_fwy);
-    slab.zeros((size_t)nfield * (2 * spec[1].P + 2) * nx, &plan->d_fiface1_next);
-    slab.zeros((size_t)2 * nfield * spec[0].P * spec[1].P * 4, &plan->d_fsums);
-    slab.zeros((size_t)nfield * spec[0].P * spec[1].P * 4, &plan->d_ftsums);
+  if (form >= STEPS_FUSED) slab.zeros(xrows, &fs.ix_next);
+  if (form == STEPS_ONEPASS) {
+    slab.upload_owned(std::move(phi), slab.mut(&fs.op.phi));
+    slab.upload_owned(std::move(wy), slab.mut(&fs.op.wy));
+    slab.zeros(yrows, &fs.iy_next);
+    slab.zeros(nsums, &fs.sums[0]);
+    slab.zeros(nsums, &fs.sums[1]);
+    slab.zeros(nsums, &fs.op.tsums);
   }
-  f.bsrc = nullptr;
-  f.bscale = 0.0;
-  plan->fine = true;      // the view's pointers are bound after SlabBuilder::commit (rect_plan_create_impl)
+  return true;
 }
 
-// the passes of qp_adi_rect_phase on the fine view (interfaces always decoupled: the reduced phases are empty)
-static int fine_phase(qp_adi_rect_plan* plan, int phase, double* u, hipStream_t stream) {
-  const FineView& f = plan->fview;
-  const unsigned tiles = (unsigned)((long)f.nfield * (f.ny / 64) * f.px);     // = nfield * py * (nx / 64)
-  double* w = plan->d_work;
-  switch (phase) {
-    case QP_ADI_ENTRY:
-      QP_LAUNCH_FINE(f.stream, fine_y_kernel, 0, dim3(tiles), dim3(64), 0, stream, f, (const double*)u, w);
-      break;
-    case QP_ADI_REDUCED_X:
-    case QP_ADI_REDUCED_Y:
-      break;
-    case QP_ADI_SWEEP_X:
-      QP_LAUNCH_FINE(f.stream, fine_x_kernel, true, dim3(tiles), dim3(64), 0, stream, f, w);
-      break;
-    case QP_ADI_SWEEP_Y_CARRY:
-      QP_LAUNCH_FINE(f.stream, fine_y_kernel, 1, dim3(tiles), dim3(64), 0, stream, f, (const double*)w, w);
-      break;
-    case QP_ADI_SWEEP_Y_EXIT:
-      QP_LAUNCH_FINE(f.stream, fine_y_kernel, 2, dim3(tiles), dim3(64), 0, stream, f, (const double*)w, u);
-      break;
-    default:
-      set_error("qp_adi_rect_phase: unknown phase %d", phase);
-      return QP_ERR_INVALID_ARGUMENT;
+// The fused step forms ping-pong their interface rows: step s reads the x-interface rows (and, on one-pass plans, the
+// y-interface rows) from buffer s % 2 - this view - and writes buffer (s + 1) % 2.  ENTRY writes buffer 0.
+static FineView fine_step_view(const FineState& fs, int s) {
+  FineView f = fs.view;
+  if (s & 1) {
+    f.iface[0] = fs.ix_next;
+    if (fs.form == STEPS_ONEPASS) f.iface[1] = fs.iy_next;
   }
-  return check_launch("qp_adi_rect_phase (fine tiles)");
+  return f;
 }
 
 // qp_adi_rect_steps on a fused plan: ENTRY, then per step the reduce pass R (reads rhs1, leaves iface[1]) and the fused
 // pass F (reads rhs1 again, leaves rhs1' in place and the x-interface rows of the next step; the solution on the last step).
-// Step s reads the x-interface rows from buffer s % 2 and writes buffer (s + 1) % 2; ENTRY writes buffer 0.
-static int fine_steps_fused(qp_adi_rect_plan* plan, double* u, int nsteps, hipStream_t stream) {
-  FineView f = plan->fview;
-  const unsigned tiles = (unsigned)((long)f.nfield * (f.ny / 64) * f.px);
+static int fine_steps_fused(qp_adi_rect_plan* plan, double* u, int nsteps, hipStream_t st) {
+  const FineState& fs = plan->fine;
   double* w = plan->d_work;
-  double* const ix[2] = {plan->d_fiface[0], plan->d_fiface0_next};
-  f.iface[0] = ix[0];
-  QP_LAUNCH_FINE(f.stream, fine_y_kernel, 0, dim3(tiles), dim3(64), 0, stream, f, (const double*)u, w);
+  launch_y<0>(fs.view, u, w, st);
   for (int s = 0; s < nsteps; ++s) {
-    f.iface[0] = ix[s & 1];
-    double* next = ix[(s + 1) & 1];
-    if (f.stream == 0) hipLaunchKernelGGL((fine_reduce_kernel<0>), dim3(tiles), dim3(64), 0, stream, f, (const double*)w);
-    else if (f.stream == 2) hipLaunchKernelGGL((fine_reduce_kernel<2>), dim3(tiles), dim3(64), 0, stream, f, (const double*)w);
-    else hipLaunchKernelGGL((fine_reduce_kernel<3>), dim3(tiles), dim3(64), 0, stream, f, (const double*)w);
-    if (s + 1 < nsteps) QP_LAUNCH_FINE(f.stream, fine_fused_kernel, 1, dim3(tiles), dim3(64), 0, stream, f, next, w, w);
-    else QP_LAUNCH_FINE(f.stream, fine_fused_kernel, 2, dim3(tiles), dim3(64), 0, stream, f, next, w, u);
+    const FineView f = fine_step_view(fs, s);
+    double* ix_next = fine_step_view(fs, s + 1).iface[0];
+    launch_fine_reduce(f, w, st);
+    if (s + 1 < nsteps) launch_fine_fused<1>(f, ix_next, w, w, st);
+    else launch_fine_fused<2>(f, ix_next, w, u, st);
   }
   return check_launch("qp_adi_rect_steps (fused fine tiles)");
 }
@@ -895,34 +969,22 @@ static int fine_steps_fused(qp_adi_rect_plan* plan, double* u, int nsteps, hipSt
 // <1>: the fused pass plus P of the next step's y-interface rows and the tile sums T of the x-interface rows it writes)
 // and the ghost-sum pass X of the next step (T -> S, one thread per chunk pair), and on the last step the exit form of F'.
 // The entry pass leaves no T: step 0 takes the all-zero sums, and every later step's S comes from the F' before it.
-// Step s reads the x-interface rows from ix[s % 2] and the y-interface rows from iy[s % 2] (full rows after R on step 0,
-// with the all-zero sums; P form after that), and writes buffer (s + 1) % 2 of both.
-static int fine_steps_onepass(qp_adi_rect_plan* plan, double* u, int nsteps, hipStream_t stream) {
-  FineView f = plan->fview;
-  const unsigned tiles = (unsigned)((long)f.nfield * (f.ny / 64) * f.px);
+// Step 0 reads full y-interface rows (after R, with the all-zero sums), every later step rows in P form.
+static int fine_steps_onepass(qp_adi_rect_plan* plan, double* u, int nsteps, hipStream_t st) {
+  const FineState& fs = plan->fine;
   double* w = plan->d_work;
-  double* const ix[2] = {plan->d_fiface[0], plan->d_fiface0_next};
-  double* const iy[2] = {plan->d_fiface[1], plan->d_fiface1_next};
-  double* const sums = plan->d_fsums + (size_t)f.nfield * f.px * f.py * 4;
-  FineOnePass op{plan->d_fphi, nullptr, nullptr, plan->d_fwy, plan->d_ftsums};
-  const unsigned nsum = (unsigned)(((long)f.nfield * f.px * f.py + 255) / 256);
-  f.iface[0] = ix[0];
-  f.iface[1] = iy[0];
-  QP_LAUNCH_FINE(f.stream, fine_y_kernel, 0, dim3(tiles), dim3(64), 0, stream, f, (const double*)u, w);
-  if (f.stream == 0) hipLaunchKernelGGL((fine_reduce_kernel<0>), dim3(tiles), dim3(64), 0, stream, f, (const double*)w);
-  else if (f.stream == 2) hipLaunchKernelGGL((fine_reduce_kernel<2>), dim3(tiles), dim3(64), 0, stream, f, (const double*)w);
-  else hipLaunchKernelGGL((fine_reduce_kernel<3>), dim3(tiles), dim3(64), 0, stream, f, (const double*)w);
+  FineOnePass op = fs.op;
+  launch_y<0>(fs.view, u, w, st);
+  launch_fine_reduce(fs.view, w, st);
   for (int s = 0; s < nsteps; ++s) {
-    f.iface[0] = ix[s & 1];
-    f.iface[1] = iy[s & 1];
-    double* next = ix[(s + 1) & 1];
-    op.p_next = iy[(s + 1) & 1];
-    op.sums = s == 0 ? plan->d_fsums : sums;
+    const FineView f = fine_step_view(fs, s), next = fine_step_view(fs, s + 1);
+    op.p_next = next.iface[1];
+    op.sums = fs.sums[s == 0 ? 0 : 1];
     if (s + 1 < nsteps) {
-      QP_LAUNCH_FINE(f.stream, fine_onepass_kernel, 1, dim3(tiles), dim3(64), 0, stream, f, next, w, w, op);
-      hipLaunchKernelGGL(fine_ghostsum_kernel, dim3(nsum), dim3(256), 0, stream, f, (const double*)plan->d_ftsums, sums);
+      launch_fine_onepass<1>(f, next.iface[0], w, w, op, st);
+      launch_fine_ghostsum(f, op.tsums, fs.sums[1], st);
     } else {
-      QP_LAUNCH_FINE(f.stream, fine_onepass_kernel, 2, dim3(tiles), dim3(64), 0, stream, f, next, w, u, op);
+      launch_fine_onepass<2>(f, next.iface[0], w, u, op, st);
     }
   }
   return check_launch("qp_adi_rect_steps (one-pass fine tiles)");
@@ -994,18 +1056,14 @@ static int rect_plan_create_impl(int32_t ny, int32_t nx, int32_t nfield, double 
     alpha[b] = a;
     for (int d = 0; d < 2; ++d) {
       const int P = spec[d].P;
-      // representative global chunk per variant: interior -> 1, first -> 0, last -> P-1, single -> 0
       for (int var = 0; var < 4; ++var) {
-        int p;
-        if (var == 0) { if (P < 3) continue; p = 1; }
-        else if (var == 1) { if (P < 2) continue; p = 0; }
-        else if (var == 2) { if (P < 2) continue; p = P - 1; }
-        else { if (P != 1) continue; p = 0; }
+        const int p = variant_chunk(var, P);
+        if (p < 0) continue;
         double ends[4];
         double* tb = &tab[((((size_t)d * nfield + b) * 4 + var) * T_NSLOT) * TS];
-        build_chunk_table(spec[d], a, p, tb, ends);
-        all_compact = all_compact && table_is_compact(tb);
-        build_compact_table(tb, &ctab[(((size_t)d * nfield + b) * 4 + var) * 2 * CT_PART]);
+        build_chunk_table(spec[d], a, p, TS, tb, ends);
+        all_compact = all_compact && table_is_compact(TS, tb);
+        build_compact_table(TS, tb, &ctab[(((size_t)d * nfield + b) * 4 + var) * 2 * CT_PART]);
       }
       far[d] = std::max(far[d], reduced_tables(spec[d], a, p0[d], ploc[d],
                                                split[d] ? nullptr : &lu[d][(size_t)b * 5 * 2 * P],
@@ -1021,10 +1079,10 @@ static int rect_plan_create_impl(int32_t ny, int32_t nx, int32_t nfield, double 
               far[0], far[1], kFarCouplingDrop);
     return QP_ERR_UNSUPPORTED;
   }
-  SlabBuilder slab;
-  slab.upload(alpha, &plan->d_alpha);
-  slab.upload(tab, &plan->d_tab);
-  slab.upload(ctab, &plan->d_ctab);
+  SlabBuilder slab;      // binds every device pointer of the two views at commit
+  slab.upload(alpha, slab.mut(&v.alpha));
+  slab.upload(tab, slab.mut(&v.tab));
+  slab.upload(ctab, slab.mut(&v.ctab));
   v.compact = all_compact ? 1 : 0;
   if (const char* e = getenv("QPSIM_COMPACT_TABLES")) v.compact = v.compact && atoi(e) != 0;   // 0: force the full form
   v.bsrc = nullptr;
@@ -1032,17 +1090,18 @@ static int rect_plan_create_impl(int32_t ny, int32_t nx, int32_t nfield, double 
   plan->pr_scale = pr_scale;
   // fine tiles first: a plan that runs them needs no interface arrays for the 64 x 64 kernels when it is the plan of a
   // Peaceman-Rachford iteration (nothing else ever runs on it)
-  if (!decomposed && force_banded == 0 && ny % 64 == 0 && nx % 64 == 0 &&
-      (pr_scale != 0.0 ? fine_tiles_allowed() : fine_tiles_wanted(nfield, ny, nx)))
-    fine_plan_prepare(plan, r, dcoef_host, spec, slab);
-  const bool lean = pr_scale != 0.0 && plan->fine;
+  if (!decomposed && force_banded == 0 && ny % 64 == 0 && nx % 64 == 0 && fine_tiles_wanted(pr_scale != 0.0, nfield, ny, nx)) {
+    const int form = fine_step_form(plan);
+    if (fine_plan_prepare(plan, form, alpha, spec, slab)) plan->fine.form = form;
+  }
+  const bool lean = pr_scale != 0.0 && plan->fine.on();
   for (int d = 0; d < 2; ++d) {
     const size_t nlines = d == 0 ? ny : nx;
-    slab.upload(lu[d], &plan->d_lu[d]);
-    slab.upload(icoef[d], &plan->d_icoef[d]);
-    slab.zeros(lean ? 1 : (size_t)nfield * (2 * ploc[d] + 2) * nlines, &plan->d_iface[d]);
-    slab.zeros(lean ? 1 : (size_t)nfield * 2 * ploc[d] * nlines, &plan->d_z[d]);
-    slab.zeros(lean ? 1 : (size_t)nfield * nx, &plan->d_uhalo[d]);
+    slab.upload(lu[d], slab.mut(&v.lu[d]));
+    slab.upload(icoef[d], slab.mut(&v.icoef[d]));
+    slab.zeros(lean ? 1 : (size_t)nfield * (2 * ploc[d] + 2) * nlines, &v.iface[d]);
+    slab.zeros(lean ? 1 : (size_t)nfield * 2 * ploc[d] * nlines, &v.z[d]);
+    slab.zeros(lean ? 1 : (size_t)nfield * nx, slab.mut(&v.uhalo[d]));
   }
   bool ok = slab.commit(&plan->d_slab);
   if (share) {
@@ -1056,25 +1115,6 @@ static int rect_plan_create_impl(int32_t ny, int32_t nx, int32_t nfield, double 
     qp_adi_rect_plan_destroy(plan);
     set_error("qp_adi_rect_plan_create: device allocation or upload failed");
     return QP_ERR_ALLOC;
-  }
-  v.alpha = plan->d_alpha;
-  v.tab = plan->d_tab;
-  v.ctab = plan->d_ctab;
-  for (int d = 0; d < 2; ++d) {
-    v.lu[d] = plan->d_lu[d];
-    v.icoef[d] = plan->d_icoef[d];
-    v.iface[d] = plan->d_iface[d];
-    v.z[d] = plan->d_z[d];
-    v.uhalo[d] = plan->d_uhalo[d];
-  }
-  if (plan->fine) {
-    FineView& f = plan->fview;
-    f.alpha = plan->d_alpha;
-    f.ctab = plan->d_fctab;
-    for (int d = 0; d < 2; ++d) {
-      f.icoef[d] = plan->d_ficoef[d];
-      f.iface[d] = plan->d_fiface[d];
-    }
   }
   *out = plan;
   return QP_OK;
@@ -1115,7 +1155,7 @@ int qp_adi_rect_pr_cycle(qp_adi_rect_plan* const* plans, int32_t nplans, double*
     QP_REQUIRE(plans[j] && plans[j]->pr_scale != 0.0, "not a Peaceman-Rachford plan (qp_adi_rect_plan_create_pr)");
     QP_REQUIRE(plans[j]->ncell == plans[0]->ncell && plans[j]->view.d.nfield == plans[0]->view.d.nfield &&
                    plans[j]->view.d.nx == plans[0]->view.d.nx, "the plans of a cycle must have one shape");
-    carried = carried && plans[j]->fine;
+    carried = carried && plans[j]->fine.on();
   }
   if (const char* e = getenv("QPSIM_PR_CARRIED")) carried = carried && atoi(e) != 0;
   if (!carried) {
@@ -1127,60 +1167,36 @@ int qp_adi_rect_pr_cycle(qp_adi_rect_plan* const* plans, int32_t nplans, double*
   }
   hipStream_t stream = (hipStream_t)stream_;
   double* w = plans[0]->d_work;
-  const FineView& f0 = plans[0]->fview;
-  const unsigned tiles = (unsigned)((long)f0.nfield * (f0.ny / 64) * f0.px);
-  auto view = [&](int j) {
-    FineView f = plans[j]->fview;
-    f.bsrc = b;
-    f.bscale = plans[j]->pr_scale;
-    return f;
-  };
+  auto view = [&](int j) { return with_source(plans[j]->fine.view, b, plans[j]->pr_scale); };
   FineView cur = view(0);
-  QP_LAUNCH_FINE_SRC(cur.stream, fine_y_kernel, 0, dim3(tiles), dim3(64), 0, stream, cur, (const double*)u, w);
+  launch_y<0, true>(cur, u, w, stream);
   for (int j = 0; j < nplans; ++j) {
-    QP_LAUNCH_FINE_SRC(cur.stream, fine_x_kernel, true, dim3(tiles), dim3(64), 0, stream, cur, w);
+    launch_x<true, true>(cur, w, stream);
     if (j + 1 < nplans) {
       const FineView nxt = view(j + 1);
-      if (cur.stream == 0) hipLaunchKernelGGL((fine_y_next_kernel<0>), dim3(tiles), dim3(64), 0, stream, cur, nxt, w);
-      else if (cur.stream == 2) hipLaunchKernelGGL((fine_y_next_kernel<2>), dim3(tiles), dim3(64), 0, stream, cur, nxt, w);
-      else hipLaunchKernelGGL((fine_y_next_kernel<3>), dim3(tiles), dim3(64), 0, stream, cur, nxt, w);
+      launch_fine_y_next(cur, nxt, w, stream);
       cur = nxt;
     } else {
-      QP_LAUNCH_FINE(cur.stream, fine_y_kernel, 2, dim3(tiles), dim3(64), 0, stream, cur, (const double*)w, u);
+      launch_y<2>(cur, w, u, stream);
     }
   }
   return check_launch("qp_adi_rect_pr_cycle");
 }
 
 // u <- one Peaceman-Rachford iteration towards A u = b (see qp_adi_rect_plan_create_pr), u and b [nfield][ny*nx].
+// Fine tiles where the plan has them; otherwise 64 x 64 tiles: any extents, banded reduced systems where the chunks do not
+// decouple (those passes report under the name of the phase API).
 int qp_adi_rect_pr_iteration(qp_adi_rect_plan* plan, double* u, const double* b, void* stream_) {
   QP_REQUIRE(plan && u && b, "plan, u, b must be non-NULL");
   QP_REQUIRE(plan->pr_scale != 0.0, "not a Peaceman-Rachford plan (qp_adi_rect_plan_create_pr)");
   using namespace qp;
   hipStream_t stream = (hipStream_t)stream_;
-  if (!plan->fine) {      // 64 x 64 tiles: any extents, banded reduced systems where the chunks do not decouple
-    RectView v = plan->view;
-    v.bsrc = b;
-    v.bscale = plan->pr_scale;
-    const unsigned ctiles = (unsigned)((long)v.d.nfield * v.d.py * v.d.px);
-    double* cw = plan->d_work;
-    QP_LAUNCH_STREAMED_SRC(v.d.stream, v.compact, rect_y_kernel, 0, dim3(ctiles), dim3(64), 0, stream, v, (const double*)u, cw);
-    int rc = qp_adi_rect_phase(plan, QP_ADI_REDUCED_X, u, stream_);
-    if (rc) return rc;
-    QP_LAUNCH_STREAMED_SRC(v.d.stream, v.compact, rect_x_kernel, true, dim3(ctiles), dim3(64), 0, stream, v, cw);
-    rc = qp_adi_rect_phase(plan, QP_ADI_REDUCED_Y, u, stream_);
-    if (rc) return rc;
-    return qp_adi_rect_phase(plan, QP_ADI_SWEEP_Y_EXIT, u, stream_);
+  if (plan->fine.on()) {
+    three_passes<0, true, true>(with_source(plan->fine.view, b, plan->pr_scale), u, plan->d_work, u, stream);
+    return check_launch("qp_adi_rect_pr_iteration");
   }
-  FineView f = plan->fview;
-  f.bsrc = b;
-  f.bscale = plan->pr_scale;
-  const unsigned tiles = (unsigned)((long)f.nfield * (f.ny / 64) * f.px);
-  double* w = plan->d_work;
-  QP_LAUNCH_FINE_SRC(f.stream, fine_y_kernel, 0, dim3(tiles), dim3(64), 0, stream, f, (const double*)u, w);
-  QP_LAUNCH_FINE_SRC(f.stream, fine_x_kernel, true, dim3(tiles), dim3(64), 0, stream, f, w);
-  QP_LAUNCH_FINE(f.stream, fine_y_kernel, 2, dim3(tiles), dim3(64), 0, stream, f, (const double*)w, u);
-  return check_launch("qp_adi_rect_pr_iteration");
+  three_passes<0, true, true>(with_source(plan->view, b, plan->pr_scale), u, plan->d_work, u, stream);
+  return check_launch("qp_adi_rect_phase");
 }
 
 int qp_adi_rect_plan_create(int32_t ny, int32_t nx, int32_t nfield, double r, const double* dcoef_host,
@@ -1194,57 +1210,31 @@ int qp_adi_rect_plan_decoupled(const qp_adi_rect_plan* plan, int32_t dir) {
   return plan->view.decoupled[dir];
 }
 
-int qp_adi_rect_plan_fine(const qp_adi_rect_plan* plan) { return plan && plan->fine ? 1 : 0; }
+int qp_adi_rect_plan_fine(const qp_adi_rect_plan* plan) { return plan && plan->fine.on() ? 1 : 0; }
 
 int qp_adi_rect_phase(qp_adi_rect_plan* plan, int32_t phase, double* u, void* stream_) {
   QP_REQUIRE(plan != nullptr, "plan is NULL");
+  QP_REQUIRE(u != nullptr || (phase != QP_ADI_ENTRY && phase != QP_ADI_SWEEP_Y_EXIT), "u is NULL");
   using namespace qp;
   hipStream_t stream = (hipStream_t)stream_;
-  if (plan->fine) {
-    QP_REQUIRE(u != nullptr || (phase != QP_ADI_ENTRY && phase != QP_ADI_SWEEP_Y_EXIT), "u is NULL");
-    return fine_phase(plan, phase, u, stream);
+  const bool fine = plan->fine.on();
+  if (!(fine ? run_phase(plan->fine.view, phase, u, plan->d_work, stream)
+             : run_phase(plan->view, phase, u, plan->d_work, stream))) {
+    set_error("qp_adi_rect_phase: unknown phase %d", phase);
+    return QP_ERR_INVALID_ARGUMENT;
   }
-  const RectView& v = plan->view;
-  const unsigned tiles = (unsigned)((long)v.d.nfield * v.d.py * v.d.px);
-  double* w = plan->d_work;
-  switch (phase) {
-    case QP_ADI_ENTRY:
-      QP_REQUIRE(u != nullptr, "u is NULL");
-      QP_LAUNCH_STREAMED(v.d.stream, v.compact, rect_y_kernel, 0, dim3(tiles), dim3(64), 0, stream, v, (const double*)u, w);
-      break;
-    case QP_ADI_REDUCED_X:
-      if (!v.decoupled[0])
-        hipLaunchKernelGGL(rect_reduced_kernel, dim3((unsigned)(((long)v.d.ny * v.d.nfield + 63) / 64)), dim3(64), 0,
-                           stream, v, 0);
-      break;
-    case QP_ADI_SWEEP_X:
-      QP_LAUNCH_STREAMED(v.d.stream, v.compact, rect_x_kernel, true, dim3(tiles), dim3(64), 0, stream, v, w);
-      break;
-    case QP_ADI_REDUCED_Y:
-      if (!v.decoupled[1])
-        hipLaunchKernelGGL(rect_reduced_kernel, dim3((unsigned)(((long)v.d.nx * v.d.nfield + 63) / 64)), dim3(64), 0,
-                           stream, v, 1);
-      break;
-    case QP_ADI_SWEEP_Y_CARRY:
-      QP_LAUNCH_STREAMED(v.d.stream, v.compact, rect_y_kernel, 1, dim3(tiles), dim3(64), 0, stream, v, (const double*)w, w);
-      break;
-    case QP_ADI_SWEEP_Y_EXIT:
-      QP_REQUIRE(u != nullptr, "u is NULL");
-      QP_LAUNCH_STREAMED(v.d.stream, v.compact, rect_y_kernel, 2, dim3(tiles), dim3(64), 0, stream, v, (const double*)w, u);
-      break;
-    default:
-      set_error("qp_adi_rect_phase: unknown phase %d", phase);
-      return QP_ERR_INVALID_ARGUMENT;
-  }
-  return check_launch("qp_adi_rect_phase");
+  return check_launch(fine ? "qp_adi_rect_phase (fine tiles)" : "qp_adi_rect_phase");
 }
 
 int qp_adi_rect_steps(qp_adi_rect_plan* plan, double* u, int32_t nsteps, void* stream) {
   QP_REQUIRE(plan && u, "plan and u must be non-NULL");
   QP_REQUIRE(nsteps >= 1, "nsteps must be >= 1");
   QP_REQUIRE(!plan->decomposed, "a decomposed plan needs halo exchanges between phases: drive it with qp_adi_rect_phase");
-  if (plan->fine && plan->fused == 2) return qp::fine_steps_onepass(plan, u, nsteps, (hipStream_t)stream);
-  if (plan->fine && plan->fused) return qp::fine_steps_fused(plan, u, nsteps, (hipStream_t)stream);
+  switch (plan->fine.form) {
+    case qp::STEPS_ONEPASS: return qp::fine_steps_onepass(plan, u, nsteps, (hipStream_t)stream);
+    case qp::STEPS_FUSED: return qp::fine_steps_fused(plan, u, nsteps, (hipStream_t)stream);
+    default: break;      // two sweeps per step, on either tile family: the phases
+  }
   int rc = qp_adi_rect_phase(plan, QP_ADI_ENTRY, u, stream);
   for (int s = 0; s < nsteps && rc == QP_OK; ++s) {
     rc = qp_adi_rect_phase(plan, QP_ADI_REDUCED_X, u, stream);
@@ -1262,23 +1252,11 @@ int qp_adi_rect_solve(qp_adi_rect_plan* plan, double* x, void* stream_) {
   QP_REQUIRE(!plan->decomposed, "qp_adi_rect_solve is not available on decomposed plans");
   using namespace qp;
   hipStream_t stream = (hipStream_t)stream_;
-  if (plan->fine) {
-    const FineView& f = plan->fview;
-    const unsigned ftiles = (unsigned)((long)f.nfield * (f.ny / 64) * f.px);
-    QP_LAUNCH_FINE(f.stream, fine_y_kernel, 3, dim3(ftiles), dim3(64), 0, stream, f, (const double*)x, x);
-    QP_LAUNCH_FINE(f.stream, fine_x_kernel, false, dim3(ftiles), dim3(64), 0, stream, f, x);
-    QP_LAUNCH_FINE(f.stream, fine_y_kernel, 2, dim3(ftiles), dim3(64), 0, stream, f, (const double*)x, x);
+  if (plan->fine.on()) {
+    three_passes<3, false, false>(plan->fine.view, x, x, x, stream);
     return check_launch("qp_adi_rect_solve (fine tiles)");
   }
-  const RectView& v = plan->view;
-  const unsigned tiles = (unsigned)((long)v.d.nfield * v.d.py * v.d.px);
-  QP_LAUNCH_STREAMED(v.d.stream, v.compact, rect_y_kernel, 3, dim3(tiles), dim3(64), 0, stream, v, (const double*)x, x);
-  int rc = qp_adi_rect_phase(plan, QP_ADI_REDUCED_X, x, stream_);
-  if (rc) return rc;
-  QP_LAUNCH_STREAMED(v.d.stream, v.compact, rect_x_kernel, false, dim3(tiles), dim3(64), 0, stream, v, x);
-  rc = qp_adi_rect_phase(plan, QP_ADI_REDUCED_Y, x, stream_);
-  if (rc) return rc;
-  QP_LAUNCH_STREAMED(v.d.stream, v.compact, rect_y_kernel, 2, dim3(tiles), dim3(64), 0, stream, v, (const double*)x, x);
+  three_passes<3, false, false>(plan->view, x, x, x, stream);
   return check_launch("qp_adi_rect_solve");
 }
 
@@ -1309,12 +1287,12 @@ int qp_adi_rect_combine(qp_adi_rect_plan* plan, const double* u, const double* r
   if (v.d.nx == 1) { g.dr = 0.0; g.sr = 0.0; }   // one column: rect_side_terms folds both x-faces into the "left" slot
   if (v.d.ny == 1) { g.dd = 0.0; g.sd = 0.0; }
   double* part = (out == nullptr || norm_out) ? (double*)workspace : nullptr;
-#define QP_COMBINE(STORE, RB)                                                                                              \
-  hipLaunchKernelGGL((rect_combine_kernel<STORE, RB>), dim3((unsigned)blocks), dim3(256), 0, stream, v.d.ny, v.d.nx,      \
-                     v.d.nfield, (const double*)plan->d_alpha, g, u, rin, out, c0, cx, cy, cs, cr, part)
-  if (out) { if (small) QP_COMBINE(true, 4); else QP_COMBINE(true, 8); }
-  else { if (small) QP_COMBINE(false, 4); else QP_COMBINE(false, 8); }
-#undef QP_COMBINE
+  with_bool(out != nullptr, [&](auto STORE) {
+    with_bool(small, [&](auto SMALL) {
+      hipLaunchKernelGGL((rect_combine_kernel<decltype(STORE)::value, decltype(SMALL)::value ? 4 : 8>), dim3((unsigned)blocks),
+                         dim3(256), 0, stream, v.d.ny, v.d.nx, v.d.nfield, v.alpha, g, u, rin, out, c0, cx, cy, cs, cr, part);
+    });
+  });
   if (norm_out) absmax_finish((const double*)workspace, (int)blocks, norm_out, stream);
   return check_launch("qp_adi_rect_combine");
 }
@@ -1335,7 +1313,7 @@ int qp_adi_rect_iface_halo(qp_adi_rect_plan* plan, int32_t dir, int32_t side, in
   size_t row;
   if (op == 0) row = side == 0 ? 1 : 2 * (size_t)P;
   else row = side == 0 ? 0 : 2 * (size_t)P + 1;
-  double* strided = plan->d_iface[dir] + row * nlines;
+  double* strided = v.iface[dir] + row * nlines;
   const size_t w = nlines * sizeof(double), pitch = rows * nlines * sizeof(double);
   hipError_t e = op == 0
                      ? hipMemcpy2DAsync(buf, w, strided, pitch, w, v.d.nfield, hipMemcpyDeviceToDevice, (hipStream_t)stream)
@@ -1352,7 +1330,7 @@ int qp_adi_rect_set_field_halo(qp_adi_rect_plan* plan, int32_t side, const doubl
   QP_REQUIRE(plan && rows && (side == 0 || side == 1), "bad arguments");
   QP_REQUIRE(plan->decomposed && plan->pr_scale == 0.0, "only plans of qp_adi_rect_plan_create_block on a decomposed grid take field halo rows");
   const qp::RectView& v = plan->view;
-  hipError_t e = hipMemcpyAsync(plan->d_uhalo[side], rows, (size_t)v.d.nfield * v.d.nx * sizeof(double),
+  hipError_t e = hipMemcpyAsync(const_cast<double*>(v.uhalo[side]), rows, (size_t)v.d.nfield * v.d.nx * sizeof(double),
                                 hipMemcpyDeviceToDevice, (hipStream_t)stream);
   if (e != hipSuccess) {
     qp::set_error("qp_adi_rect_set_field_halo: %s", hipGetErrorString(e));

@@ -721,9 +721,9 @@ static int tile_plan_create(int32_t ny, int32_t nx, int32_t nfield, double r, co
   for (int b = 0; b < nfield && !var; ++b) {
     alpha[b] = r * dcoef_host[b];
     double ends[4];
-    build_chunk_table(spec, alpha[b], 1, &tab[(size_t)b * T_NSLOT * TS], ends);
-    all_compact = all_compact && table_is_compact(&tab[(size_t)b * T_NSLOT * TS]);
-    build_compact_table(&tab[(size_t)b * T_NSLOT * TS], &ctab[(size_t)b * 2 * CT_PART]);
+    build_chunk_table(spec, alpha[b], 1, TS, &tab[(size_t)b * T_NSLOT * TS], ends);
+    all_compact = all_compact && table_is_compact(TS, &tab[(size_t)b * T_NSLOT * TS]);
+    build_compact_table(TS, &tab[(size_t)b * T_NSLOT * TS], &ctab[(size_t)b * 2 * CT_PART]);
   }
 
   auto* plan = new qp_adi_tile_plan();

@@ -43,13 +43,12 @@ __host__ __device__ constexpr int slot_pre(int slot) {
 __host__ __device__ constexpr int slot_suf(int slot) { return (slot == T_EV || slot == T_EAV) ? 16 : 1; }
 // an entry of the constant stretch [pre, L - suf) of a slot
 __host__ __device__ constexpr int slot_mid(int L, int slot) { return (slot == T_EV || slot == T_EAV) ? L - 17 : 16; }
-inline bool table_is_compact_len(int L, const double* tab) {
+inline bool table_is_compact(int L, const double* tab) {
   for (int q = 0; q < T_NSLOT; ++q)
     for (int k = slot_pre(q); k < L - slot_suf(q); ++k)
       if (tab[q * L + k] != tab[q * L + slot_mid(L, q)]) return false;
   return true;
 }
-inline bool table_is_compact(const double* tab) { return table_is_compact_len(TS, tab); }
 // Compact table = two parts of CT_PART doubles (solve slots T_W..T_SRC, elimination slots T_EW..T_EAV): the 16-entry
 // prefixes / suffixes, then per slot its middle value, its last (or first) entry.  cidx maps (slot, k) into its part.
 constexpr int CT_PART = 72;
@@ -68,12 +67,11 @@ __host__ __device__ constexpr int cidx_len(int L, int slot, int k) {
   return 64 + q;                                                        // middle: 64..67
 }
 __host__ __device__ constexpr int cidx(int slot, int k) { return cidx_len(TS, slot, k); }
-inline void build_compact_table_len(int L, const double* tab, double* ct) {       // ct[2][CT_PART]
+inline void build_compact_table(int L, const double* tab, double* ct) {       // ct[2][CT_PART]
   for (int i = 0; i < 2 * CT_PART; ++i) ct[i] = 0.0;
   for (int q = 0; q < T_NSLOT; ++q)
     for (int k = 0; k < L; ++k) ct[(q < T_EW ? 0 : CT_PART) + cidx_len(L, q, k)] = tab[q * L + k];
 }
-inline void build_compact_table(const double* tab, double* ct) { build_compact_table_len(TS, tab, ct); }
 
 // Tables are written once at plan creation and never by a kernel: read them through the constant address space so
 // that wave-uniform accesses become scalar loads (s_load) and the values feed the FMAs straight from SGPRs.
@@ -325,8 +323,8 @@ __device__ __forceinline__ void add_source_cols(const double* __restrict__ base,
   }
 }
 
-// host: fills the T_NSLOT x TS table of chunk `p` of a line described by (n, P, end-face terms); returns
-// g[0], g[last], h[0], h[last] through `ends`
+// host: fills the T_NSLOT x L table of chunk `p` of a line described by (n, P, end-face terms) and cut into chunks of L
+// cells (TS, or FS for the fine tiles); returns g[0], g[last], h[0], h[last] through `ends`
 struct DirSpec {
   int n;          // line length
   int P;          // chunks
@@ -334,6 +332,6 @@ struct DirSpec {
   double s_lo, s_hi;   // BC sources of the two end faces
   double c0_shift = 0.0;   // explicit operator (I + a L) - c0_shift I (Peaceman-Rachford iteration plans)
 };
-void build_chunk_table(const DirSpec& s, double a, int p, double* tab, double ends[4]);
+void build_chunk_table(const DirSpec& s, double a, int p, int L, double* tab, double ends[4]);
 
 }  // namespace qp
