@@ -157,6 +157,15 @@ typedef struct qp_collision_tables {
 #define QP_COLL_FORCE_GENERIC 1u
 #define QP_COLL_FORCE_WAVE 2u
 #define QP_COLL_SHARED_BINS 4u
+/* Member classes (ensemble parameter sweeps): class k owns the contiguous cells [k * ncell / nclass,
+ * (k + 1) * ncell / nclass), kr0 / ks0 / rho hold one table per class and cls (required: the kernels without a member-table
+ * form read it) agrees with that.  ncell % nclass != 0 or cls == NULL: QP_ERR_INVALID_ARGUMENT before any launch.  Where
+ * qp_collision_member_tables_available(ne) is 1, (ncell / nclass) % 64 == 0, diag_bin / anti_bin are given and no FORCE bit
+ * is set, the single-pass register kernel runs with every wave reading its own class's tables (bit-equal to one call per
+ * class with that class's single table), and the double half-step call accepts the tables unless QP_COLL_SHARED_BINS is
+ * set.  Everything else runs the one-wave-per-pixel or the generic kernel through cls, and the double half-step call returns
+ * QP_ERR_UNSUPPORTED.  gap_sq / kr_amp / ks_amp / pair_inv / ks0_diag / kr0_anti2 are not used with this flag. */
+#define QP_COLL_MEMBER_CLASSES 8u
 
 /*
  * One local coupled quasiparticle-phonon collision update of every interior cell
@@ -196,7 +205,8 @@ int qp_collision_step_guarded(const qp_collision_tables* t, const uint8_t* flags
  * registers).  out_vals / out_idx: guard statistics of the INTERMEDIATE state (before the generation term), as
  * qp_pauli_stats.  gen_amount: dt_{k+1} * rate for constant / active pulse generation, 0 otherwise.
  * Returns QP_ERR_UNSUPPORTED (nothing launched, nothing written) when no fused kernel fits - qp_collision_pair_available(ne)
- * is 0, more than one gap class, merged phonon bins (QP_COLL_SHARED_BINS), no diag_bin / anti_bin, a FORCE flag, no enabled
+ * is 0, more than one gap class (other than member classes, see QP_COLL_MEMBER_CLASSES), merged phonon bins
+ * (QP_COLL_SHARED_BINS), no diag_bin / anti_bin, a FORCE flag, no enabled
  * process: the caller then issues the two calls above.  guard_workspace: qp_collision_guard_workspace_bytes(ncell).
  */
 int qp_collision_pair_available(int32_t ne);
@@ -214,6 +224,9 @@ int qp_collision_register_kernel_available(int32_t ne);
 int qp_collision_onepass_available(int32_t ne);
 /* 1 when the register-resident kernel also has its gap-class variant for `ne` (single-pass sizes: ne <= 16, 18, 20, 24, 30). */
 int qp_collision_register_kernel_classes(int32_t ne);
+/* 1 when the single-pass and the double half-step register kernels are instantiated in their member-table form
+ * (QP_COLL_MEMBER_CLASSES) for `ne`: ne = 4 ... 16. */
+int qp_collision_member_tables_available(int32_t ne);
 
 /*
  * Explicit fixed-bath collision helpers of the reference's step API (not on its time loop; API parity):

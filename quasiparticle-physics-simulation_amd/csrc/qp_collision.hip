@@ -146,6 +146,12 @@ bool collision_pair_dispatch(const qp_collision_tables& tb, const uint8_t* flags
                              double* ph, double dE, double dt_a, double dt_b, double gen, bool s, bool r, bool u,
                              PauliPartial* guard, double guard_floor, hipStream_t stream);
 int collision_fast_supported(int ne);
+int collision_member_tables_supported(int ne);
+bool collision_fast_dispatch_members(int ne, int nclass, const double* kr0, const double* ks0, const double* rho,
+                                     const int* diag_bin, const int* anti_bin, double* stash, const uint8_t* flags,
+                                     long ncell, const double* sin_, double* sout, double* ph, double dE, double dt, int en_r,
+                                     int en_s, int upd, PauliPartial* guard, double guard_floor, bool* guard_done,
+                                     hipStream_t stream);
 int collision_fast_classes_supported(int ne);
 bool collision_fast_dispatch_classes(int ne, const double* rho, const int* cls, const double* gap_sq, const double* kr_amp,
                                      const double* ks_amp, const double* pair_inv, const int* diag_bin, const int* anti_bin,
@@ -171,6 +177,21 @@ bool collision_wave_dispatch(const WaveCollView& v, bool structured, const uint8
 
 }  // namespace qp
 
+// QP_COLL_MEMBER_CLASSES: the cells divide evenly among the classes, and the class map of the fallback kernels is there
+static int member_classes_ok(const qp_collision_tables* t, int64_t ncell, const char* who) {
+  if (!(t->flags & QP_COLL_MEMBER_CLASSES)) return 1;
+  if (t->nclass <= 0 || ncell % t->nclass != 0) {
+    qp::set_error("%s: QP_COLL_MEMBER_CLASSES needs ncell (%lld) to be a multiple of nclass (%d)", who, (long long)ncell,
+                  t->nclass);
+    return 0;
+  }
+  if (!t->cls) {
+    qp::set_error("%s: QP_COLL_MEMBER_CLASSES needs cls (the kernels without member tables read it)", who);
+    return 0;
+  }
+  return 1;
+}
+
 static int collision_step_impl(const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
                                const double* state_in, double* state_out, double* phonon, double* ph_scratch,
                                double dE, double dt, int enable_recombination, int enable_scattering,
@@ -189,6 +210,8 @@ static int collision_step_impl(const qp_collision_tables* t, const uint8_t* flag
   QP_REQUIRE(flags && state_in && state_out && phonon, "flags, state_in, state_out, phonon must be non-NULL");
   QP_REQUIRE(state_in != state_out, "state_in and state_out must not alias");
   QP_REQUIRE(ncell > 0, "ncell must be positive");
+  if (!member_classes_ok(t, ncell, "qp_collision_step")) return QP_ERR_INVALID_ARGUMENT;
+  const bool member_classes = (t->flags & QP_COLL_MEMBER_CLASSES) && t->nclass > 1;
   const bool no_scratch_ok = !(t->flags & QP_COLL_FORCE_GENERIC) && t->ne <= 64 && t->nw <= 192;
   QP_REQUIRE(!(update_phonons && (enable_recombination || enable_scattering)) || ph_scratch || no_scratch_ok,
              "ph_scratch is required when phonons are updated by the generic kernel");
@@ -210,8 +233,17 @@ static int collision_step_impl(const qp_collision_tables* t, const uint8_t* flag
                                   state_in, state_out, phonon, dE, dt, enable_recombination, enable_scattering,
                                   update_phonons, guard, guard_floor, guard_done, (hipStream_t)stream))
     return qp::check_launch("qp_collision_step(fast)");
+  // one table per ensemble member: the register kernels that pick the wave's table (aligned members, ne = 4 ... 16); every
+  // other member-class table runs the one-wave-per-pixel or generic kernel below through `cls`
+  if (member_classes && t->diag_bin && !(t->flags & (QP_COLL_FORCE_GENERIC | QP_COLL_FORCE_WAVE)) && shared_ok &&
+      qp::collision_member_tables_supported(t->ne) &&
+      qp::collision_fast_dispatch_members(t->ne, t->nclass, t->kr0, t->ks0, t->rho, t->diag_bin, t->anti_bin, ph_scratch,
+                                          flags, (long)ncell, state_in, state_out, phonon, dE, dt, enable_recombination,
+                                          enable_scattering, update_phonons, guard, guard_floor, guard_done,
+                                          (hipStream_t)stream))
+    return qp::check_launch("qp_collision_step(fast, member classes)");
   // gap classes with the separable kernel tables: the one-pass kernel where it exists ...
-  if (t->diag_bin && t->nclass > 1 && qp::collision_onepass_supported(t->ne) &&
+  if (t->diag_bin && t->nclass > 1 && !member_classes && qp::collision_onepass_supported(t->ne) &&
       !(t->flags & (QP_COLL_FORCE_GENERIC | QP_COLL_FORCE_WAVE)) && shared_ok && ncell < (1L << 28) &&
       qp::collision_onepass_dispatch_classes(*t, ph_scratch, flags, (long)ncell, state_in, state_out, phonon, dE, dt,
                                              enable_scattering && t->ks0, enable_recombination && t->kr0,
@@ -219,7 +251,7 @@ static int collision_step_impl(const qp_collision_tables* t, const uint8_t* flag
                                              (hipStream_t)stream))
     return qp::check_launch("qp_collision_step(one pass, gap classes)");
   // ... else the register kernels that form K per pixel
-  if (t->diag_bin && t->nclass > 1 && t->gap_sq && t->pair_inv && t->cls &&
+  if (t->diag_bin && t->nclass > 1 && !member_classes && t->gap_sq && t->pair_inv && t->cls &&
       (!(enable_recombination && t->kr0) || t->kr_amp) && (!(enable_scattering && t->ks0) || t->ks_amp) &&
       !(t->flags & (QP_COLL_FORCE_GENERIC | QP_COLL_FORCE_WAVE)) && shared_ok &&
       qp::collision_fast_dispatch_classes(t->ne, t->rho, t->cls, t->gap_sq, enable_recombination ? t->kr_amp : nullptr,
@@ -354,6 +386,7 @@ extern "C" int qp_collision_double_step_guarded(const qp_collision_tables* t, co
   QP_REQUIRE(flags && state_in && state_out && phonon && state_in != state_out, "flags, state_in, state_out (distinct), phonon");
   QP_REQUIRE(guard_workspace && out_vals && out_idx, "guard_workspace, out_vals, out_idx must be non-NULL");
   QP_REQUIRE(ncell > 0 && t->rho != nullptr, "ncell must be positive, rho non-NULL");
+  if (!member_classes_ok(t, ncell, "qp_collision_double_step_guarded")) return QP_ERR_INVALID_ARGUMENT;
   const bool s = enable_scattering && t->ks0, r = enable_recombination && t->kr0;
   auto* parts = (qp::PauliPartial*)guard_workspace;
   if (!qp::collision_pair_dispatch(*t, flags, (long)ncell, state_in, state_out, phonon, dE, dt_first, dt_second, gen_amount, s, r,
@@ -366,6 +399,9 @@ extern "C" int qp_collision_double_step_guarded(const qp_collision_tables* t, co
   qp::pauli_finish(parts + qp::kGuardMergeBlocks, nparts, parts, out_vals, (long*)out_idx, (hipStream_t)stream);
   return qp::check_launch("qp_collision_double_step_guarded");
 }
+
+// 1 when the single-pass and double half-step register kernels exist in their member-table form (QP_COLL_MEMBER_CLASSES)
+extern "C" int qp_collision_member_tables_available(int32_t ne) { return qp::collision_member_tables_supported(ne); }
 
 extern "C" int qp_collision_onepass_available(int32_t ne) { return qp::collision_onepass_supported(ne); }
 
@@ -426,6 +462,7 @@ extern "C" int qp_collision_double_step_guarded_members(const qp_collision_table
   QP_REQUIRE(guard_workspace && out_vals && out_idx, "guard_workspace, out_vals, out_idx must be non-NULL");
   QP_REQUIRE(ncell > 0 && t->rho != nullptr, "ncell must be positive, rho non-NULL");
   if (!members_args_ok(ncell, ncell_member, members, "qp_collision_double_step_guarded_members")) return QP_ERR_INVALID_ARGUMENT;
+  if (!member_classes_ok(t, ncell, "qp_collision_double_step_guarded_members")) return QP_ERR_INVALID_ARGUMENT;
   if (ncell_member % 64 != 0) {
     qp::set_error("qp_collision_double_step_guarded_members: ncell_member (%lld) is not a multiple of 64",
                   (long long)ncell_member);

@@ -88,6 +88,43 @@ bool collision_fast_dispatch_classes(int ne, const double* rho, const int* cls, 
   return true;
 }
 
+// Member classes (QP_COLL_MEMBER_CLASSES): kr0 / ks0 / rho hold `nclass` tables and class k owns the cells
+// [k ncell / nclass, (k + 1) ncell / nclass).  False when this NE has no member-table instantiation or a wave would straddle
+// two classes; the caller has checked ncell % nclass == 0.
+QP_MEMBER_NE_LIST(QP_DECLARE_DIAGM)
+bool collision_fast_dispatch_members(int ne, int nclass, const double* kr0, const double* ks0, const double* rho,
+                                     const int* diag_bin, const int* anti_bin, double* stash, const uint8_t* flags,
+                                     long ncell, const double* sin_, double* sout, double* ph, double dE, double dt, int en_r,
+                                     int en_s, int upd, PauliPartial* guard, double guard_floor, bool* guard_done,
+                                     hipStream_t stream) {
+  if (guard_done) *guard_done = false;
+  if (ncell >= (1L << 28) || nclass < 1 || (ncell / nclass) % 64 != 0) return false;
+  const bool s = en_s && ks0, r = en_r && kr0, u = upd && (s || r);
+  if (!s && !r) return false;       // no process: the shared-table dispatcher's copy kernel serves any tables
+  CollFastViewM v{{kr0, ks0, rho, diag_bin, anti_bin, stash, nullptr, nullptr, nullptr, nullptr, nullptr, guard, guard_floor},
+                  (unsigned)(ncell / nclass), (unsigned)nclass};
+  diag_launcherm_t fn = nullptr;
+  switch (ne) {
+#define QP_CASE(N) case N: fn = (s && r) ? diag_launcherm_##N##_11 : r ? diag_launcherm_##N##_01 : diag_launcherm_##N##_10; break;
+    QP_MEMBER_NE_LIST(QP_CASE)
+#undef QP_CASE
+    default: return false;
+  }
+  fn(v, flags, ncell, sin_, sout, ph, dE, dt, u, stream);
+  if (guard_done) *guard_done = guard != nullptr;
+  return true;
+}
+
+// 1 when the member-table variants (single pass and double half-step) exist for this NE
+int collision_member_tables_supported(int ne) {
+  switch (ne) {
+#define QP_CASE(N) case N: return 1;
+    QP_MEMBER_NE_LIST(QP_CASE)
+#undef QP_CASE
+    default: return 0;
+  }
+}
+
 // 1 when the gap-class (PARAM) variant exists for this NE
 int collision_fast_classes_supported(int ne) {
   switch (ne) {

@@ -71,6 +71,27 @@ struct CollFastView {
   double guard_floor;
 };
 
+// Member classes (QP_COLL_MEMBER_CLASSES), the argument of the MEMB kernels: class m owns the cells [m ncell_member,
+// (m + 1) ncell_member) and kr0 / ks0 / rho hold one table per class.  ncell_member is a multiple of 64, so a wave never
+// straddles two members.  (A type of its own: the kernels without MEMB keep their argument block.)
+struct CollFastViewM : CollFastView {
+  unsigned ncell_member;
+  unsigned members;
+};
+template <bool MEMB>
+struct coll_view { typedef CollFastView type; };
+template <>
+struct coll_view<true> { typedef CollFastViewM type; };
+
+// Member of the wave whose first lane holds pixel `p` (call with every lane active: the value is taken from lane 0).  Waves
+// are 64 consecutive pixels starting at a multiple of 64 and ncell_member % 64 == 0, so every pixel of the wave that lies
+// inside the grid belongs to this member; the clamp keeps the table base of a wave beyond the grid inside the allocation.
+__device__ __forceinline__ unsigned wave_member(unsigned p, unsigned ncell_member, unsigned members) {
+  const unsigned p0 = __builtin_amdgcn_readfirstlane(p);
+  const unsigned m = p0 / ncell_member;
+  return __builtin_amdgcn_readfirstlane(m < members - 1u ? m : members - 1u);
+}
+
 // butterfly over the 64 lanes of a wave (all lanes active): (f, t) -> np.argmax order, forb -> smallest index >= 0
 __device__ __forceinline__ void guard_wave_reduce(double& f, long& t, long& forb) {
 #pragma unroll
@@ -218,9 +239,10 @@ __device__ __forceinline__ double affine_update_f(double y, double a, double b, 
 
 // USE_S / USE_R / UPD are compile-time: with run-time flags the compiler clones and threads the unrolled body into
 // flag-specific paths whose instructions it then interleaves across diagonals (several phonon values live at once).
-template <int NE, bool USE_S, bool USE_R, bool UPD, bool PARAM = false>
+// MEMB: per-member tables (CollFastViewM); the wave takes its member's rho / K^s_0 / K^r_0, everything else is the same.
+template <int NE, bool USE_S, bool USE_R, bool UPD, bool PARAM = false, bool MEMB = false>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(NE <= 12 ? 4 : 1, 8)))
-collision_diag_kernel(CollFastView t, const uint8_t* __restrict__ flags,
+collision_diag_kernel(typename coll_view<MEMB>::type t, const uint8_t* __restrict__ flags,
                                                              long ncell, const double* __restrict__ sin_,
                                                              double* __restrict__ sout, double* __restrict__ ph,
                                                              double dE, double dt) {
@@ -230,13 +252,16 @@ collision_diag_kernel(CollFastView t, const uint8_t* __restrict__ flags,
   double gf = -__builtin_huge_val();
   long gt = 0x7fffffffffffffffL, gforb = -1;
   const bool in_grid = p < (unsigned long)ncell;
+  // before the branches below, where all 64 lanes are still active
+  unsigned long mb = 0;
+  if constexpr (MEMB) mb = wave_member(p, t.ncell_member, t.members);
   if (in_grid && !(flags[p] & QP_FLAG_ACTIVE)) {
 #pragma unroll
     for (int i = 0; i < NE; ++i) (sout + (long)i * ncell)[p] = (sin_ + (long)i * ncell)[p];
   } else if (in_grid) {
-  const cdtab_t rho = uniform_const<cdtab_t>(t.rho);
-  const cdtab_t ks = uniform_const<cdtab_t>(t.ks0);
-  const cdtab_t kr = uniform_const<cdtab_t>(t.kr0);
+  const cdtab_t rho = uniform_const<cdtab_t>(MEMB ? t.rho + mb * NE : t.rho);
+  const cdtab_t ks = uniform_const<cdtab_t>(MEMB ? t.ks0 + mb * (NE * NE) : t.ks0);
+  const cdtab_t kr = uniform_const<cdtab_t>(MEMB ? t.kr0 + mb * (NE * NE) : t.kr0);
   const citab_t dbin = uniform_const<citab_t>(t.diag_bin);
   const citab_t abin = uniform_const<citab_t>(t.anti_bin);
   const cdtab_t ec = exp_table();
@@ -655,6 +680,37 @@ static void launch_srp(const CollFastView& v, const uint8_t* flags, long ncell, 
   }
 #define QP_DEFINE_DIAGP(N) QP_DEFINE_DIAGP_SR(N, 1, 1) QP_DEFINE_DIAGP_SR(N, 0, 1) QP_DEFINE_DIAGP_SR(N, 1, 0)
 
+// Member-class variant (collision_diag_kernel<..., false, true>): the sizes of the double half-step kernel, NE <= 16.
+template <int NE, bool S, bool R>
+static void launch_srm(const CollFastViewM& v, const uint8_t* flags, long ncell, const double* sin_, double* sout, double* ph,
+                       double dE, double dt, bool u, hipStream_t stream) {
+  const unsigned blocks = (unsigned)((ncell + 127) / 128);
+  if (u)
+    hipLaunchKernelGGL((collision_diag_kernel<NE, S, R, true, false, true>), dim3(blocks), dim3(128), 0, stream, v, flags,
+                       ncell, sin_, sout, ph, dE, dt);
+  else
+    hipLaunchKernelGGL((collision_diag_kernel<NE, S, R, false, false, true>), dim3(blocks), dim3(128), 0, stream, v, flags,
+                       ncell, sin_, sout, ph, dE, dt);
+}
+
+#define QP_DEFINE_DIAGM_SR(N, S, R)                                                                                      \
+  void diag_launcherm_##N##_##S##R(const CollFastViewM& v, const uint8_t* flags, long ncell, const double* sin_,         \
+                                   double* sout, double* ph, double dE, double dt, bool u, hipStream_t stream) {         \
+    launch_srm<N, S != 0, R != 0>(v, flags, ncell, sin_, sout, ph, dE, dt, u, stream);                                   \
+  }
+#define QP_DEFINE_DIAGM(N) QP_DEFINE_DIAGM_SR(N, 1, 1) QP_DEFINE_DIAGM_SR(N, 0, 1) QP_DEFINE_DIAGM_SR(N, 1, 0)
+#define QP_DECLARE_DIAGM(N)                                                                                               \
+  void diag_launcherm_##N##_11(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,\
+                               bool, hipStream_t);                                                                         \
+  void diag_launcherm_##N##_01(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,\
+                               bool, hipStream_t);                                                                         \
+  void diag_launcherm_##N##_10(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,\
+                               bool, hipStream_t);
+// the NE with a member-class instantiation (single-pass and double half-step kernel alike)
+#define QP_MEMBER_NE_LIST(X) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
+
+typedef void (*diag_launcherm_t)(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,
+                                 bool, hipStream_t);
 typedef void (*diag_launcher_t)(const CollFastView&, const uint8_t*, long, const double*, double*, double*, double, double,
                                 bool, hipStream_t);
 

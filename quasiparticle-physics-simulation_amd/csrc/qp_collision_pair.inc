@@ -21,23 +21,26 @@
 
 namespace qp {
 
-template <int NE, bool USE_S, bool USE_R, bool UPD>
+// MEMB: per-member tables, selected per wave as in collision_diag_kernel.
+template <int NE, bool USE_S, bool USE_R, bool UPD, bool MEMB = false>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu((NE <= 12 && UPD) ? 3 : 2)))
-collision_pair_kernel(CollFastView t, const uint8_t* __restrict__ flags, long ncell, const double* __restrict__ sin_,
-                      double* __restrict__ sout, double* __restrict__ ph, double dE, double dt_a, double dt_b,
-                      double gen_amount) {
+collision_pair_kernel(typename coll_view<MEMB>::type t, const uint8_t* __restrict__ flags, long ncell,
+                      const double* __restrict__ sin_, double* __restrict__ sout, double* __restrict__ ph, double dE,
+                      double dt_a, double dt_b, double gen_amount) {
   __shared__ double lds[(USE_R && UPD) ? (2 * NE - 1) * 128 : 1];
   const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
   double gf = -__builtin_huge_val();
   long gt = 0x7fffffffffffffffL, gforb = -1;
   const bool in_grid = p < (unsigned long)ncell;
+  unsigned long mb = 0;
+  if constexpr (MEMB) mb = wave_member(p, t.ncell_member, t.members);      // all 64 lanes still active
   if (in_grid && !(flags[p] & QP_FLAG_ACTIVE)) {
 #pragma unroll
     for (int i = 0; i < NE; ++i) (sout + (long)i * ncell)[p] = (sin_ + (long)i * ncell)[p];
   } else if (in_grid) {
-    const cdtab_t rho = uniform_const<cdtab_t>(t.rho);
-    const cdtab_t ks = uniform_const<cdtab_t>(t.ks0);
-    const cdtab_t kr = uniform_const<cdtab_t>(t.kr0);
+    const cdtab_t rho = uniform_const<cdtab_t>(MEMB ? t.rho + mb * NE : t.rho);
+    const cdtab_t ks = uniform_const<cdtab_t>(MEMB ? t.ks0 + mb * (NE * NE) : t.ks0);
+    const cdtab_t kr = uniform_const<cdtab_t>(MEMB ? t.kr0 + mb * (NE * NE) : t.kr0);
     const citab_t dbin = uniform_const<citab_t>(t.diag_bin);
     const citab_t abin = uniform_const<citab_t>(t.anti_bin);
     const cdtab_t ec = exp_table();
@@ -191,19 +194,22 @@ collision_pair_kernel(CollFastView t, const uint8_t* __restrict__ flags, long nc
   }
 }
 
+typedef void (*pair_launcherm_t)(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,
+                                 double, double, bool, hipStream_t);
 typedef void (*pair_launcher_t)(const CollFastView&, const uint8_t*, long, const double*, double*, double*, double, double,
                                 double, double, bool, hipStream_t);
 
-template <int NE, bool S, bool R>
-static void pair_launch(const CollFastView& v, const uint8_t* flags, long ncell, const double* sin_, double* sout, double* ph,
-                        double dE, double dt_a, double dt_b, double gen, bool u, hipStream_t stream) {
+template <int NE, bool S, bool R, bool MEMB = false>
+static void pair_launch(const typename coll_view<MEMB>::type& v, const uint8_t* flags, long ncell, const double* sin_,
+                        double* sout, double* ph, double dE, double dt_a, double dt_b, double gen, bool u,
+                        hipStream_t stream) {
   const unsigned blocks = (unsigned)((ncell + 127) / 128);
   if (u)
-    hipLaunchKernelGGL((collision_pair_kernel<NE, S, R, true>), dim3(blocks), dim3(128), 0, stream, v, flags, ncell, sin_, sout,
-                       ph, dE, dt_a, dt_b, gen);
+    hipLaunchKernelGGL((collision_pair_kernel<NE, S, R, true, MEMB>), dim3(blocks), dim3(128), 0, stream, v, flags, ncell,
+                       sin_, sout, ph, dE, dt_a, dt_b, gen);
   else
-    hipLaunchKernelGGL((collision_pair_kernel<NE, S, R, false>), dim3(blocks), dim3(128), 0, stream, v, flags, ncell, sin_,
-                       sout, ph, dE, dt_a, dt_b, gen);
+    hipLaunchKernelGGL((collision_pair_kernel<NE, S, R, false, MEMB>), dim3(blocks), dim3(128), 0, stream, v, flags, ncell,
+                       sin_, sout, ph, dE, dt_a, dt_b, gen);
 }
 
 #define QP_DEFINE_PAIR(N)                                                                                                  \
@@ -219,5 +225,27 @@ static void pair_launch(const CollFastView& v, const uint8_t* flags, long ncell,
                               double dE, double da, double db, double g, bool u, hipStream_t s) {                          \
     pair_launch<N, true, false>(v, f, nc, si, so, ph, dE, da, db, g, u, s);                                                \
   }
+
+// member-class variant: qp::pair_launcherm_<N>_<S><R>
+#define QP_DEFINE_PAIRM(N)                                                                                                 \
+  void pair_launcherm_##N##_11(const CollFastViewM& v, const uint8_t* f, long nc, const double* si, double* so, double* ph, \
+                               double dE, double da, double db, double g, bool u, hipStream_t s) {                         \
+    pair_launch<N, true, true, true>(v, f, nc, si, so, ph, dE, da, db, g, u, s);                                           \
+  }                                                                                                                        \
+  void pair_launcherm_##N##_01(const CollFastViewM& v, const uint8_t* f, long nc, const double* si, double* so, double* ph, \
+                               double dE, double da, double db, double g, bool u, hipStream_t s) {                         \
+    pair_launch<N, false, true, true>(v, f, nc, si, so, ph, dE, da, db, g, u, s);                                          \
+  }                                                                                                                        \
+  void pair_launcherm_##N##_10(const CollFastViewM& v, const uint8_t* f, long nc, const double* si, double* so, double* ph, \
+                               double dE, double da, double db, double g, bool u, hipStream_t s) {                         \
+    pair_launch<N, true, false, true>(v, f, nc, si, so, ph, dE, da, db, g, u, s);                                          \
+  }
+#define QP_DECLARE_PAIRM(N)                                                                                                \
+  void pair_launcherm_##N##_11(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,\
+                               double, double, bool, hipStream_t);                                                         \
+  void pair_launcherm_##N##_01(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,\
+                               double, double, bool, hipStream_t);                                                         \
+  void pair_launcherm_##N##_10(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,\
+                               double, double, bool, hipStream_t);
 
 }  // namespace qp

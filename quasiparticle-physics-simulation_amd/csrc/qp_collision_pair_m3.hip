@@ -1,0 +1,8 @@
+// Double half-step collision kernels with per-member tables (QP_COLL_MEMBER_CLASSES), NE = 15, 16 (see
+// qp_collision_pair.inc).
+#include "qp_collision_pair.inc"
+
+namespace qp {
+QP_DEFINE_PAIRM(15)
+QP_DEFINE_PAIRM(16)
+}  // namespace qp

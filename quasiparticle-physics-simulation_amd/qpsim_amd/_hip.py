@@ -116,6 +116,7 @@ SIGNATURES = {
     "qp_collision_register_kernel_available": (C.c_int, [C.c_int32]),
     "qp_collision_register_kernel_classes": (C.c_int, [C.c_int32]),
     "qp_collision_onepass_available": (C.c_int, [C.c_int32]),
+    "qp_collision_member_tables_available": (C.c_int, [C.c_int32]),
     "qp_collision_pair_available": (C.c_int, [C.c_int32]),
     "qp_collision_double_step_guarded": (C.c_int, [C.POINTER(CollisionTables), c_dp, C.c_int64, c_dp, c_dp, c_dp, C.c_double,
                                                    C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double,

@@ -826,13 +826,17 @@ class Engine:
 
     # -- collisions, generation, reductions -------------------------------------------------------------------
     def make_collision_tables(self, kr0, ks0, rho, idx_diff, idx_sum, sign, cls_packed=None, allow_fast=True,
-                              kernel: str = "auto", gap_params: dict | None = None, members: int = 1):
+                              kernel: str = "auto", gap_params: dict | None = None, members: int = 1,
+                              member_classes: bool = False):
         """Upload per-gap-class tables ([C,NE,NE], [C,NE]) and maps; returns an opaque handle.
 
         ``kernel``: "auto" | "generic" | "wave" | "wave_unstructured" forces a collision kernel (tests, A/B timing).
         ``gap_params`` (gap classes only): ``dict(E=E_bins, gaps=class_gaps, tau_r=, tau_s=, T_c=)`` - lets the register
         kernel form K^r_0, K^s_0 per pixel from gap-independent tables (they are separable in the gap).
-        ``members`` > 1: the class map is repeated over an ensemble laid out [member][cell] (same tables for every member)."""
+        ``members`` > 1: the class map is repeated over an ensemble laid out [member][cell] (same tables for every member).
+        ``member_classes``: the C tables are one set per ensemble member instead (``QP_COLL_MEMBER_CLASSES``: ``members``
+        = C, class m = the cells of member m).  The register kernels read them for NE = 4 ... 16 when a member's cell count
+        is a multiple of 64; other shapes and larger NE run the one-wave-per-pixel kernel through the class map."""
         torch = self.torch
         up = lambda a, dt: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.device)  # noqa: E731
         rho = np.atleast_2d(np.asarray(rho, dtype=np.float64))
@@ -842,7 +846,14 @@ class Engine:
              "rho": up(rho, np.float64), "idx_diff": up(idx_diff, np.int32), "idx_sum": up(idx_sum, np.int32),
              "sign": up(sign, np.int8), "cls": None, "ne": ne, "nclass": nclass}
         nw = int(max(np.max(idx_diff), np.max(idx_sum))) + 1
-        if nclass > 1:
+        if member_classes:
+            if nclass != int(members):
+                raise ValueError("member classes need one table set per member")
+            h["cls"] = up(np.repeat(np.arange(nclass, dtype=np.int32), self.ncell), np.int32)
+            gap_params = None
+            if kernel == "auto" and os.environ.get("QPSIM_MEMBER_TABLES", "1") == "0":      # A/B timing: class-map kernels
+                kernel = "wave"
+        elif nclass > 1:
             if cls_packed is None:
                 raise ValueError("cls is required for more than one gap class")
             full = np.zeros(self.ncell, dtype=np.int32)
@@ -871,7 +882,8 @@ class Engine:
         h["symmetric"] = bool(symmetric)
         if (not allow_fast or not symmetric) and kernel == "auto":
             kernel = "generic"
-        flag_bits = {"auto": 0, "generic": 1, "wave": 2, "wave_unstructured": 2}[kernel] | (4 if shared else 0)
+        flag_bits = ({"auto": 0, "generic": 1, "wave": 2, "wave_unstructured": 2}[kernel] | (4 if shared else 0)
+                     | (8 if member_classes else 0))
         if kernel == "wave_unstructured":
             kernel = "wave"
         wave_ok = ne <= 64 and nw <= 192
@@ -892,8 +904,13 @@ class Engine:
                 np.fill_diagonal(ksa, 0.0)
                 h["ks_amp"] = up(ksa, np.float64)
             classes_ok = True
+        # member classes: the register kernels' member-table form where it exists, decided per call by the member's cell
+        # count (the merged-bin stash is sized for it either way)
+        members_ok = bool(member_classes and self.lib.qp_collision_member_tables_available(ne))
+        h["member_classes"] = bool(member_classes)
         h["kernel"] = ("generic" if (kernel == "generic" or not wave_ok) else
-                       "register" if (kernel == "auto" and structure is not None and (nclass == 1 or classes_ok)
+                       "register" if (kernel == "auto" and structure is not None
+                                      and (members_ok if member_classes else (nclass == 1 or classes_ok))
                                       and bool(self.lib.qp_collision_register_kernel_available(ne))) else "wave")
         h["fast"] = h["kernel"] != "generic"      # no accumulator planes needed
         # one-pass kernel (ne = 30, 32, 40, 50): the kernel tables once more in (anti)diagonal-major order (qpsim_hip.h)
@@ -904,7 +921,8 @@ class Engine:
             if kr0 is not None:
                 h["kr0_anti2"] = up(antidiagonal_major(np.asarray(kr0).reshape(ne, ne), 2.0), np.float64)
         # consecutive half-steps of neighbouring Strang steps in one pass (qp_collision_double_step_guarded)
-        h["pair"] = bool(h["kernel"] == "register" and nclass == 1 and structure is not None and not shared and symmetric
+        h["pair"] = bool(h["kernel"] == "register" and (nclass == 1 or members_ok) and structure is not None and not shared
+                         and symmetric
                          and kernel == "auto" and self.lib.qp_collision_pair_available(ne)
                          and os.environ.get("QPSIM_COLL_PAIR", "1") != "0")
         h["struct"] = _hip.CollisionTables.make(ne, nw, nclass, _ptr(h["kr0"]), _ptr(h["ks0"]), _ptr(h["rho"]),

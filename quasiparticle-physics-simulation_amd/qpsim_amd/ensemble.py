@@ -6,6 +6,13 @@ diffusion plan sees NE * M fields and the collision kernels M * ncell pixels, an
 Pauli guard is reduced per member on the device (``qp_pauli_stats_members`` and the ``*_guarded_members`` collision calls),
 so every member warns and raises exactly as its lone run would, its messages prefixed ``member m: ``.
 
+Parameter sweeps: ``sweep={"tau_0": [...], "T_c": [...], ...}`` (keys of ``SWEEP_KEYS``, one value per member) varies the
+collision physics over the members.  Every member then has its own K^r_0 / K^s_0 / rho tables on the device (built on the
+host exactly as its lone run builds them); with NE = 4 ... 16 and a member cell count that is a multiple of 64 the register
+collision kernels - single pass and double half-step - read the table of the wave's member, bit-equal to the lone tables;
+other shapes and larger NE run the one-wave-per-pixel kernel through a member class map and two calls instead of the pair
+pass.  A sweep whose members all end up with the same tables runs exactly as the call without ``sweep``.
+
 Rounding: members are bit-equal to their lone ``run_2d_crank_nicolson`` call with ``diffusion_scheme="adi"`` when both use
 the same ADI tile family (``QPSIM_FINE_TILES``) and the same step form (``QPSIM_ADI_FUSED``: a batch of at least 4 Mi
 cells takes the one-pass steps, which round the interface rows differently, while a smaller lone member does not), within
@@ -24,12 +31,14 @@ from . import tables as _tb
 from .distributed import shard_members
 from .engine import Engine, _ptr
 
-__all__ = ["run_2d_crank_nicolson_ensemble", "PER_MEMBER_KEYS", "member_arguments", "plan_batches",
+__all__ = ["run_2d_crank_nicolson_ensemble", "PER_MEMBER_KEYS", "SWEEP_KEYS", "member_arguments", "plan_batches",
            "generation_amounts", "last_run_stats"]
 
 # keys a member may set for itself; everything else is shared by the ensemble
 PER_MEMBER_KEYS = ("initial_field", "energy_weights", "initial_condition_spec", "external_generation", "bath_temperature",
                    "diffusion_coefficient", "phonon_history_out", "progress_callback")
+# shared keys that ``sweep=`` may vary over the members (one value per member): the collision physics
+SWEEP_KEYS = ("tau_0", "tau_s", "tau_r", "T_c", "dynes_gamma")
 _STATS: dict = {}
 
 
@@ -38,10 +47,42 @@ def last_run_stats() -> dict:
     return dict(_STATS)
 
 
-def member_arguments(members: list[dict], common: dict) -> list[dict]:
-    """Complete keyword sets of ``run_2d_crank_nicolson`` per member (defaults applied).  Raises ``ValueError`` naming the
-    key when a member sets a shared key, or varies D / bath temperature where the auto-precompute would depend on it."""
+def _checked_sweep(sweep, nmembers: int, common: dict) -> dict:
+    """``sweep`` as {key: list of ``nmembers`` values}.  ``ValueError`` naming the key for an unknown key, a list of the
+    wrong length, a key that ``common`` sets to something else than every swept value, or a sweep next to 'precomputed' /
+    'gap_expression'."""
+    if sweep is None:
+        return {}
+    if not isinstance(sweep, dict):
+        raise TypeError("sweep must be a dict of {key: one value per member}")
+    shared_pre = common.get("precomputed") is not None or str(common.get("gap_expression", "") or "").strip()
+    out = {}
+    for key, values in sweep.items():
+        if key not in SWEEP_KEYS:
+            raise ValueError(f"sweep: '{key}' cannot be swept (sweep keys: {', '.join(SWEEP_KEYS)})")
+        if isinstance(values, (str, bytes)) or not hasattr(values, "__len__"):
+            raise ValueError(f"sweep: '{key}' needs a sequence of {nmembers} values, one per member")
+        values = list(values)
+        if len(values) != nmembers:
+            raise ValueError(f"sweep: '{key}' has {len(values)} values for {nmembers} members")
+        if shared_pre:
+            raise ValueError(f"'{key}' cannot be swept together with 'precomputed' or 'gap_expression' (the precomputed "
+                             "arrays are built from one value)")
+        if key in common and any(v != common[key] for v in values):
+            raise ValueError(f"sweep: '{key}' is also set in the common arguments to {common[key]!r}, which differs from "
+                             "its swept values; give it in one place")
+        out[key] = values
+    return out
+
+
+def member_arguments(members: list[dict], common: dict, sweep: dict | None = None) -> list[dict]:
+    """Complete keyword sets of ``run_2d_crank_nicolson`` per member (defaults applied, ``sweep[key][m]`` substituted for
+    member m).  Raises ``ValueError`` naming the key when a member sets a shared key, varies D / bath temperature where the
+    auto-precompute would depend on it, or the sweep is malformed (``_checked_sweep``).  A swept key may also stand in
+    ``common`` only with the value every member sweeps to; any other value there is refused as a conflict."""
     sig = inspect.signature(S.run_2d_crank_nicolson)
+    members = list(members)
+    sweep = _checked_sweep(sweep, len(members), common)
     out = []
     for m, over in enumerate(members):
         if not isinstance(over, dict):
@@ -51,6 +92,7 @@ def member_arguments(members: list[dict], common: dict) -> list[dict]:
                 raise ValueError(f"member {m}: '{key}' is shared by all members of an ensemble and cannot be set per "
                                  f"member (per-member keys: {', '.join(PER_MEMBER_KEYS)})")
         kw = dict(common, **over)
+        kw.update({key: values[m] for key, values in sweep.items()})
         try:
             bound = sig.bind(**kw)
         except TypeError as exc:
@@ -94,12 +136,18 @@ def _bytes_per_member(kw: dict) -> float:
     return 8.0 * ncell * (8 * ne + 3 * nw + 8)
 
 
-def run_2d_crank_nicolson_ensemble(members: list[dict], *, errors: str = "raise", max_members_per_batch: int | None = None,
-                                   process_group=None, **common) -> list:
+def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = None, errors: str = "raise",
+                                   max_members_per_batch: int | None = None, process_group=None, **common) -> list:
     """Run ``len(members)`` independent problems batched on the device.
 
     ``common`` takes the keyword arguments of ``run_2d_crank_nicolson``; ``members[m]`` overrides only the keys of
-    ``PER_MEMBER_KEYS``.  Entry m is the 6-tuple member m's lone call returns (its ``phonon_history_out`` filled the same
+    ``PER_MEMBER_KEYS``.  ``sweep`` maps keys of ``SWEEP_KEYS`` (tau_0, tau_s, tau_r, T_c, dynes_gamma) to one value per
+    member: member m runs as its lone call with ``sweep[key][m]`` in place of the common value (``tau_s`` / ``tau_r``
+    default from that member's ``tau_0``; its ``dynes_gamma`` also shapes its initial state and its Pauli guard).  A swept
+    key must not be set to another value in ``common``, and a sweep cannot be combined with ``precomputed`` or
+    ``gap_expression``.  The register collision kernels serve per-member tables for ``num_energy_bins`` 4 ... 16 when the
+    member's device grid holds a multiple of 64 cells; larger NE and other grids run the one-wave-per-pixel kernel.
+    Entry m is the 6-tuple member m's lone call returns (its ``phonon_history_out`` filled the same
     way), or - with ``errors="return"`` - the ``ValueError`` its Pauli guard raised (the other members finish).  With
     ``errors="raise"`` the first violation (earliest step, then lowest member) raises ``ValueError("member m: ...")``.
     Members run in consecutive batches when they do not all fit on the device (``max_members_per_batch`` caps a batch).
@@ -107,7 +155,7 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, errors: str = "raise"
     device and every rank returns the full list."""
     if errors not in ("raise", "return"):
         raise ValueError("errors must be 'raise' or 'return'")
-    kws = member_arguments(list(members), common)
+    kws = member_arguments(list(members), common, sweep)
     _STATS.clear()
     _STATS.update(batches=0, pair_passes=0, guarded_calls=0)
     if not kws:
@@ -186,7 +234,7 @@ def _run_batch_on_device(kws, ids, errors, device):
     stored = lambda step: step % store_every == 0 or step == total_steps  # noqa: E731
     if not a["energy_gap"] > 0.0:
         return _run_scalar_batch(eng, kws, inits, mask, rem, full_steps, total_steps, stored)
-    return _run_energy_batch(eng, kws, ids, errors, inits, mask, n, flags, tau_s_eff, tau_r_eff, rem, full_steps,
+    return _run_energy_batch(eng, kws, ids, errors, inits, mask, n, flags, [(c[4], c[5]) for c in checked], rem, full_steps,
                              total_steps, stored)
 
 
@@ -247,10 +295,24 @@ def _run_scalar_batch(eng, kws, inits, mask, rem, full_steps, total_steps, store
     return out
 
 
-def _run_energy_batch(eng, kws, ids, errors, inits, mask, n, flags, tau_s_eff, tau_r_eff, rem, full_steps, total_steps,
-                      stored):
+def table_parameters(kws: list[dict], taus: list[tuple]) -> list[tuple]:
+    """Per member what its collision tables depend on beyond the shared energy grid: (dynes_gamma, tau_r, tau_s, T_c), with
+    the entries of a disabled process blanked (they reach no table).  ``taus``: (tau_s, tau_r) as resolved per member."""
+    out = []
+    for k, (tau_s, tau_r) in zip(kws, taus):
+        en_r, en_s = bool(k["enable_recombination"]), bool(k["enable_scattering"])
+        out.append((k["dynes_gamma"], tau_r if en_r else None, tau_s if en_s else None,
+                    k["T_c"] if (en_r or en_s) else None))
+    return out
+
+
+def _run_energy_batch(eng, kws, ids, errors, inits, mask, n, flags, taus, rem, full_steps, total_steps, stored):
     """Energy-resolved mode for M members: the time loop of ``run_2d_crank_nicolson`` over [bin][member][cell] planes."""
     a, M = kws[0], len(kws)
+    tau_s_eff, tau_r_eff = taus[0]
+    tparams = table_parameters(kws, taus)
+    if all(p == tparams[0] for p in tparams):                    # one table set serves every member (no sweep, or all equal)
+        tparams = None
     lib, ncm = eng.lib, eng.ncell
     dt, dx = a["dt"], a["dx"]
     gap, NE = a["energy_gap"], a["num_energy_bins"]
@@ -294,10 +356,11 @@ def _run_energy_batch(eng, kws, ids, errors, inits, mask, n, flags, tau_s_eff, t
     omega_bins, idx_diff, idx_sum, diff_sign = S._build_phonon_frequency_map(E_bins)
     nw = omega_bins.size
     ctab, rho_tab = S._collision_tables(eng, E_bins, gap, precomputed if nonuniform else None, n, a["dynes_gamma"],
-                                        tau_r_eff, tau_s_eff, a["T_c"], en_r, en_s, idx_diff, idx_sum, diff_sign, members=M)
+                                        tau_r_eff, tau_s_eff, a["T_c"], en_r, en_s, idx_diff, idx_sum, diff_sign, members=M,
+                                        member_params=tparams, member_ids=ids)
     phonon_host = np.stack([S._initial_phonon_state(mask, omega_bins, k["bath_temperature"], k["initial_condition_spec"])
                             for k in kws], axis=1).reshape(nw * M, n)
-    state_host = np.stack([_prefixed(ids[m], S._initial_qp_state, mask, inits[m], E_bins, dE, gap, a["dynes_gamma"],
+    state_host = np.stack([_prefixed(ids[m], S._initial_qp_state, mask, inits[m], E_bins, dE, gap, k["dynes_gamma"],
                                      k["energy_weights"], k["initial_condition_spec"]) for m, k in enumerate(kws)],
                           axis=1).reshape(NE * M, n)
     state = eng.upload_packed(state_host)                        # [NE * M, ncell] = [NE][M * ncell]

@@ -378,9 +378,30 @@ def _initial_phonon_state(mask, omega_bins, bath_temperature, initial_condition_
 
 
 def _collision_tables(eng, E_bins, gap, nonuniform_pre, n, dynes_gamma, tau_r_eff, tau_s_eff, T_c, enable_recombination,
-                      enable_scattering, idx_diff, idx_sum, diff_sign, members: int = 1):
+                      enable_scattering, idx_diff, idx_sum, diff_sign, members: int = 1, member_params=None,
+                      member_ids=None):
     """(device collision tables, rho per gap class) (solver.py:1189-1238); ``nonuniform_pre``: the precomputed arrays of a
-    non-uniform gap (one class per distinct gap value), None for one gap."""
+    non-uniform gap (one class per distinct gap value), None for one gap.  ``member_params`` (ensemble parameter sweeps, one
+    gap): ``(dynes_gamma, tau_r, tau_s, T_c)`` per member - one table set per member, each built exactly as that member's
+    lone run builds its own, uploaded as member classes; the rho returned is then [members, NE]."""
+    if member_params is not None:
+        built: dict = {}
+        for j, key in enumerate(member_params):
+            if key in built:
+                continue
+            gamma, tau_r, tau_s, tc = key
+            try:
+                built[key] = (_dynes_density_of_states(E_bins, float(gap), gamma),
+                              recombination_kernel_base(E_bins, float(gap), tau_r, tc) if enable_recombination else None,
+                              scattering_kernel_base(E_bins, float(gap), tau_s, tc) if enable_scattering else None)
+            except (ValueError, TypeError) as exc:
+                raise type(exc)(f"member {j if member_ids is None else member_ids[j]}: {exc}") from exc
+        rho_tab = np.stack([built[key][0] for key in member_params])
+        kr_tab = np.stack([built[key][1] for key in member_params]) if enable_recombination else None
+        ks_tab = np.stack([built[key][2] for key in member_params]) if enable_scattering else None
+        ctab = eng.make_collision_tables(kr_tab, ks_tab, rho_tab, idx_diff, idx_sum, diff_sign, None,
+                                         members=len(member_params), member_classes=True)
+        return ctab, rho_tab
     if nonuniform_pre is not None:
         gap_values = nonuniform_pre.get("gap_values")
         gap_values = np.full(n, gap, dtype=float) if gap_values is None else np.asarray(gap_values, dtype=float)

@@ -2,8 +2,14 @@
 """ms per step of the ensemble API `run_2d_crank_nicolson_ensemble`:
   (a) at the c4 shape (64 members x 256^2, NE = 12, full physics, dynamic phonons) next to the `--workload c4` loop that
       drives the same kernels with one global guard;
-  (b) 512 members x 64^2 at NE = 50 next to 512 sequential lone `run_2d_crank_nicolson` calls.
-Each figure is the difference of two run lengths (setup, first / last store excluded).  python tools/exp_ensemble.py"""
+  (b) 512 members x 64^2 at NE = 50 next to 512 sequential lone `run_2d_crank_nicolson` calls;
+  (c) a parameter sweep at the c4 shape: the same ensemble without a sweep, with `sweep={"tau_0": 64 distinct values}` (the
+      register kernels read per-member tables) and that sweep forced onto the class-map kernels (QPSIM_MEMBER_TABLES=0).
+Each figure is the difference of two run lengths (setup, first / last store excluded).
+Case (c) also times the double half-step pass alone (device events) with one shared and with per-member tables.
+python tools/exp_ensemble.py [--case all|api|sweep] [--repeat N] [--steps K]"""
+import argparse
+import os
 import sys
 import time
 import warnings
@@ -44,7 +50,89 @@ def common(N, ne):
                 diffusion_scheme="adi")
 
 
+def pair_pass_alone(repeat=1, calls=20):
+    """Device time of one double half-step pass over 64 x 256^2 pixels at NE = 12 (both processes, dynamic phonons): one
+    shared table set against 64 member table sets, alternating."""
+    from qpsim_amd import tables as T
+    from qpsim_amd.engine import CompiledGeometry, Engine, link_flags
+    N, M, ne = 256, 64, 12
+    mask = np.ones((N, N), dtype=bool)
+    z = np.zeros(mask.shape)
+    eng = Engine(CompiledGeometry(mask, 1.0, link_flags(mask), z, z, z, z))
+    ncm = eng.ncell
+    E, dE = T.build_energy_grid(180.0, 1.0, 3.0, ne)
+    om, idx_d, idx_s, sg = T.build_phonon_frequency_map(E)
+    rho = T.dynes_density_of_states(E, 180.0, 0.0)
+    tau = [300.0 + 5.0 * m for m in range(M)]
+    kr = np.stack([T.recombination_kernel_base(E, 180.0, t, 1.2) for t in tau])
+    ks = np.stack([T.scattering_kernel_base(E, 180.0, t, 1.2) for t in tau])
+    tabs = {"shared tables": eng.make_collision_tables(kr[:1], ks[:1], rho[None], idx_d, idx_s, sg),
+            "member tables": eng.make_collision_tables(kr, ks, np.tile(rho, (M, 1)), idx_d, idx_s, sg, None, members=M,
+                                                       member_classes=True)}
+    rng = np.random.default_rng(0)
+    w = rho / (rho.sum() * dE)
+    s0 = torch.as_tensor(w[:, None] * (1e-4 * (1.0 + rng.random(M * ncm)))[None, :], device=eng.device)
+    ph0 = torch.as_tensor(np.repeat(T.thermal_phonon_occupation(om, 0.1)[:, None], M * ncm, axis=1), device=eng.device)
+    out, ph = torch.empty_like(s0), ph0.clone()
+    flags = eng.d_flags.reshape(-1).repeat(M)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for r in range(repeat + 1):                                  # round 0 warms up
+        for name, tab in tabs.items():
+            assert eng.pair_members_supported(tab, ncm, M)
+            ph.copy_(ph0)
+            ev[0].record()
+            for _ in range(calls):
+                eng.collide_pair_guarded_members(tab, s0, out, ph, dE, 0.05, 0.05, 0.0, True, True, True, 1e-18, ncm, M, flags)
+            ev[1].record()
+            torch.cuda.synchronize()
+            if r:
+                print(f"double half-step pass alone, {M} x {N}^2 NE={ne}, round {r - 1}: {name}: "
+                      f"{ev[0].elapsed_time(ev[1]) / calls:.4f} ms per pass", flush=True)
+
+
+def sweep_case(repeat=1, steps=100):
+    """(c): ms/step and pair passes of the c4-shape ensemble without a sweep, with 64 distinct tau_0, and with that sweep on
+    the class-map kernels; `repeat` rounds, the three variants alternating within a round."""
+    N, M = 256, 64
+    rng = np.random.default_rng(0)
+    members = [{"initial_field": 1e-4 * (1.0 + rng.random((N, N)))} for _ in range(M)]
+    kw = common(N, 12)
+    tau = [300.0 + 5.0 * m for m in range(M)]
+    variants = [("no sweep", None, "1"), ("sweep tau_0, member tables", {"tau_0": tau}, "1"),
+                ("sweep tau_0, class-map kernels", {"tau_0": tau}, "0")]
+
+    def runner(sweep, knob):
+        def run(k):
+            os.environ["QPSIM_MEMBER_TABLES"] = knob
+            try:
+                return run_2d_crank_nicolson_ensemble(members, sweep=sweep, total_time=0.1 * k, store_every=k, **kw)
+            finally:
+                os.environ.pop("QPSIM_MEMBER_TABLES", None)
+        return run
+
+    for _, sweep, knob in variants:
+        runner(sweep, knob)(3)
+    for r in range(repeat):
+        for name, sweep, knob in variants:
+            ms = per_step(runner(sweep, knob), 5, 5 + steps)
+            print(f"c4 shape {M} x {N}^2 NE=12, round {r}: {name}: {ms:.3f} ms/step, pair passes in the {5 + steps}-step run: "
+                  f"{last_run_stats()['pair_passes']}", flush=True)
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--case", choices=["all", "api", "sweep"], default="all")
+    ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=100, help="step difference of the two run lengths of case (c)")
+    args = ap.parse_args()
+    if args.case in ("all", "api"):
+        api_cases()
+    if args.case in ("all", "sweep"):
+        sweep_case(args.repeat, args.steps)
+        pair_pass_alone(args.repeat)
+
+
+def api_cases():
     dev = torch.device("cuda", torch.cuda.current_device())
     # (a) c4 shape
     wl = W.build("c4", dev)
