@@ -228,6 +228,23 @@ int qp_collision_register_kernel_classes(int32_t ne);
  * (QP_COLL_MEMBER_CLASSES) for `ne`: ne = 4 ... 16. */
 int qp_collision_member_tables_available(int32_t ne);
 
+/* The kernel family qp_collision_step (and the step inside the guarded calls) runs for these tables, cell count and
+ * switches; have_scratch: whether ph_scratch would be non-NULL.  Launches nothing and reads only the struct itself (its
+ * pointers are tested for NULL, never followed).  Returns a QP_ROUTE_* value, or the negative status with which
+ * qp_collision_step refuses the same tables.  QPSIM_COLL_ONEPASS=0 in the environment switches the one-pass routes off. */
+typedef enum qp_collision_route_kind {
+  QP_ROUTE_ONEPASS = 0,          /* one-pass kernel, one gap class (ks0_diag / kr0_anti2) */
+  QP_ROUTE_REGISTER = 1,         /* register kernel, one gap class (ne >= 32: three launches) */
+  QP_ROUTE_REGISTER_MEMBERS = 2, /* register kernel with one table per member class */
+  QP_ROUTE_ONEPASS_CLASSES = 3,  /* one-pass kernel, gap classes */
+  QP_ROUTE_REGISTER_CLASSES = 4, /* register kernel, gap classes */
+  QP_ROUTE_WAVE = 5,             /* one wave per pixel */
+  QP_ROUTE_GENERIC = 6,          /* one thread per cell, any table */
+  QP_ROUTE_COPY = 7              /* no effective process at a register-kernel size: n' = max(n, 0) */
+} qp_collision_route_kind;
+int qp_collision_route(const qp_collision_tables* t, int64_t ncell, int enable_recombination, int enable_scattering,
+                       int update_phonons, int have_scratch);
+
 /*
  * Explicit fixed-bath collision helpers of the reference's step API (not on its time loop; API parity):
  * rhs = [g_therm - 2 n dE (K_r n)] (if kr) + [dE rho (1-f) (K_s^T n) - n dE ((K_s rho) (1-f))] (if ks), per cell;

@@ -3,7 +3,9 @@
 // Generic table-driven kernel: any NE, any phonon-bin map, per-cell gap classes.  State planes are
 // [bin][cell], so every load/store of a plane element is coalesced across the wave.  The per-cell phonon
 // accumulators a, b live in a scratch plane set [2][nw][ncell] (each thread only touches its own column).
-#include "qp_common.h"
+#include <stdlib.h>
+
+#include "qp_collision_dispatch.h"
 
 namespace qp {
 
@@ -17,23 +19,6 @@ struct CollView {
   const int8_t* sign;
   const int32_t* cls;
 };
-
-// n(t+dt) for dn/dt = gain - loss n with frozen coefficients (solver.py:640-665)
-__device__ __forceinline__ double relax_update(double n, double gain, double loss, double dt) {
-  const double mu = fmax(loss, 0.0);
-  const double P = fmax(gain + (mu - loss) * n, 0.0);
-  const double decay = exp(-mu * dt);
-  const double coeff = (mu < 1e-14) ? dt : (1.0 - decay) / mu;
-  return fmax(decay * n + coeff * P, 0.0);
-}
-
-// y(t+dt) for y' = a + b y with frozen coefficients (solver.py:686-700)
-__device__ __forceinline__ double affine_update(double y, double a, double b, double dt) {
-  const double xx = fmin(fmax(b * dt, -80.0), 80.0);
-  const double ex = exp(xx);
-  const double coeff = (fabs(b) < 1e-14) ? dt : (ex - 1.0) / b;
-  return fmax(ex * y + coeff * a, 0.0);
-}
 
 __global__ void __launch_bounds__(256) collision_generic_kernel(CollView t, const uint8_t* __restrict__ flags,
                                                                 long ncell, const double* __restrict__ sin_,
@@ -128,160 +113,181 @@ __global__ void __launch_bounds__(256) collision_generic_kernel(CollView t, cons
   }
 }
 
-bool collision_fast_dispatch(int ne, const double* kr0, const double* ks0, const double* rho, const int* diag_bin,
-                             const int* anti_bin, double* stash, const uint8_t* flags, long ncell, const double* sin_,
-                             double* sout, double* ph, double dE, double dt, int en_r, int en_s, int upd,
-                             PauliPartial* guard, double guard_floor, bool* guard_done, hipStream_t stream);
+// ---- which sizes have a launcher: generated from the lists the launchers themselves are generated from ---------------
+#define QP_DEFINE_SUPPORTED(NAME, LISTS) \
+  int NAME(int ne) {                     \
+    switch (ne) {                        \
+      LISTS return 1;                    \
+      default: return 0;                 \
+    }                                    \
+  }
+QP_DEFINE_SUPPORTED(collision_fast_supported, QP_DIAG_NE_LIST(QP_NE_CASE, _))
+QP_DEFINE_SUPPORTED(collision_fast_classes_supported, QP_DIAGP_NE_LIST(QP_NE_CASE, _) QP_DIAGP_NE_LIST_EXT(QP_NE_CASE, _))
+QP_DEFINE_SUPPORTED(collision_member_tables_supported, QP_MEMBER_NE_LIST(QP_NE_CASE, _))
+QP_DEFINE_SUPPORTED(collision_pair_supported, QP_PAIR_NE_LIST(QP_NE_CASE, _))
+QP_DEFINE_SUPPORTED(collision_onepass_supported, QP_ONEPASS_NE_LIST(QP_NE_CASE, _))
+QP_DEFINE_SUPPORTED(collision_onepass_classes_supported, QP_ONEPASS_CLASSES_NE_LIST(QP_NE_CASE, _))
 
-bool collision_onepass_dispatch(const qp_collision_tables& tb, double* stash, const uint8_t* flags, long ncell,
-                                const double* sin_, double* sout, double* ph, double dE, double dt, bool s, bool r, bool u,
-                                hipStream_t stream);
+static bool onepass_enabled() {      // QPSIM_COLL_ONEPASS=0: the three-launch split kernels (A/B timing, tests)
+  const char* e = getenv("QPSIM_COLL_ONEPASS");
+  return !e || atoi(e) != 0;
+}
 
-bool collision_onepass_dispatch_classes(const qp_collision_tables& tb, double* stash, const uint8_t* flags, long ncell,
-                                        const double* sin_, double* sout, double* ph, double dE, double dt, bool s, bool r,
-                                        bool u, hipStream_t stream);
-int collision_onepass_supported(int ne);
-int collision_pair_supported(int ne);
-bool collision_pair_dispatch(const qp_collision_tables& tb, const uint8_t* flags, long ncell, const double* sin_, double* sout,
-                             double* ph, double dE, double dt_a, double dt_b, double gen, bool s, bool r, bool u,
-                             PauliPartial* guard, double guard_floor, hipStream_t stream);
-int collision_fast_supported(int ne);
-int collision_member_tables_supported(int ne);
-bool collision_fast_dispatch_members(int ne, int nclass, const double* kr0, const double* ks0, const double* rho,
-                                     const int* diag_bin, const int* anti_bin, double* stash, const uint8_t* flags,
-                                     long ncell, const double* sin_, double* sout, double* ph, double dE, double dt, int en_r,
-                                     int en_s, int upd, PauliPartial* guard, double guard_floor, bool* guard_done,
-                                     hipStream_t stream);
-int collision_fast_classes_supported(int ne);
-bool collision_fast_dispatch_classes(int ne, const double* rho, const int* cls, const double* gap_sq, const double* kr_amp,
-                                     const double* ks_amp, const double* pair_inv, const int* diag_bin, const int* anti_bin,
-                                     double* stash, const uint8_t* flags, long ncell, const double* sin_, double* sout,
-                                     double* ph, double dE, double dt, int en_r, int en_s, int upd, PauliPartial* guard,
-                                     double guard_floor, bool* guard_done, hipStream_t stream);
+// The whole rule for which kernel family serves a single collision step, first match wins.
+Route collision_route(const qp_collision_tables& t, long ncell, bool en_r, bool en_s, bool upd, bool have_scratch) {
+  const bool s = en_s && t.ks0, r = en_r && t.kr0;       // effective processes
+  const bool member_classes = (t.flags & QP_COLL_MEMBER_CLASSES) && t.nclass > 1;
+  const bool gap_classes = t.nclass > 1 && !member_classes;
+  // merged bins (QP_COLL_SHARED_BINS): the register kernels park per-diagonal sums in ph_scratch (2 planes per merged bin);
+  // without scratch only the variants that never write phonons qualify
+  const bool shared_ok = !(t.flags & QP_COLL_SHARED_BINS) || have_scratch || !(upd && s && r);
+  // every register-resident family: structured bin maps, no FORCE bit, 32-bit pixel offsets
+  const bool reg = t.diag_bin && !(t.flags & (QP_COLL_FORCE_GENERIC | QP_COLL_FORCE_WAVE)) && shared_ok && ncell < (1L << 28);
 
-struct WaveCollView {
-  int ne, nw, nclass;
-  const double* kr0;
-  const double* ks0;
-  const double* rho;
-  const int32_t* idx_diff;
-  const int32_t* idx_sum;
-  const int8_t* sign;
-  const int32_t* cls;
-  const int32_t* diag_bin;
-  const int32_t* anti_bin;
-};
-bool collision_wave_dispatch(const WaveCollView& v, bool structured, const uint8_t* flags, long ncell, const double* sin_,
-                             double* sout, double* ph, double dE, double dt, int en_r, int en_s, int upd,
-                             hipStream_t stream);
+  if (reg && t.nclass == 1) {
+    // 32 <= ne <= 64 with the diagonal-major tables of the enabled processes: one launch instead of the three of the split
+    if (collision_onepass_supported(t.ne) && (s || r) && (!s || t.ks0_diag) && (!r || t.kr0_anti2) && onepass_enabled())
+      return QP_ROUTE_ONEPASS;
+    // no process enabled: relaxation with zero gain and loss, which the copy kernel does for any tables
+    if (collision_fast_supported(t.ne)) return (s || r) ? QP_ROUTE_REGISTER : QP_ROUTE_COPY;
+  }
+  // one table per ensemble member: the register kernels that pick the wave's table, where no wave straddles two members;
+  // every other member-class table runs the one-wave-per-pixel or generic kernel below through `cls`
+  if (reg && member_classes && collision_member_tables_supported(t.ne) && (ncell / t.nclass) % 64 == 0 && (s || r))
+    return QP_ROUTE_REGISTER_MEMBERS;
+  // gap classes with the separable kernel tables: the one-pass kernel where it exists ...
+  if (reg && gap_classes && t.cls && t.gap_sq && t.pair_inv) {
+    if (collision_onepass_classes_supported(t.ne) && t.nclass <= kOnePassMaxClasses && (s || r) && (!s || t.ks_amp) &&
+        (!r || t.kr_amp) && onepass_enabled())
+      return QP_ROUTE_ONEPASS_CLASSES;
+    // ... else the register kernels that form K per pixel; their processes are those with an amplitude table
+    if ((!r || t.kr_amp) && (!s || t.ks_amp) && ((en_s && t.ks_amp) || (en_r && t.kr_amp)) &&
+        collision_fast_classes_supported(t.ne))
+      return QP_ROUTE_REGISTER_CLASSES;
+  }
+  // NE <= 64: one wave per pixel (any class map; LDS atomics unless the host vouched for the bin-map structure)
+  if (!(t.flags & QP_COLL_FORCE_GENERIC) && t.ne <= 64 && t.nw <= 192) return QP_ROUTE_WAVE;
+  return QP_ROUTE_GENERIC;
+}
+
+// The double half-step kernel: NE = 4 ... 16, one gap class or member tables, structured unmerged bin maps, a process.
+PairRoute collision_pair_route(const qp_collision_tables& t, long ncell, bool s, bool r) {
+  const bool memb = (t.flags & QP_COLL_MEMBER_CLASSES) && t.nclass > 1;
+  if (!collision_pair_supported(t.ne) || (t.nclass != 1 && !memb) || !t.diag_bin || !t.anti_bin || !(s || r))
+    return PairRoute::None;
+  if ((t.flags & (QP_COLL_FORCE_GENERIC | QP_COLL_FORCE_WAVE | QP_COLL_SHARED_BINS)) || ncell >= (1L << 28))
+    return PairRoute::None;
+  if (!memb) return PairRoute::Shared;
+  // one table per member: no wave may straddle two members
+  const bool fits = collision_member_tables_supported(t.ne) && ncell % t.nclass == 0 && (ncell / t.nclass) % 64 == 0;
+  return fits ? PairRoute::Members : PairRoute::None;
+}
 
 }  // namespace qp
 
-// QP_COLL_MEMBER_CLASSES: the cells divide evenly among the classes, and the class map of the fallback kernels is there
-static int member_classes_ok(const qp_collision_tables* t, int64_t ncell, const char* who) {
-  if (!(t->flags & QP_COLL_MEMBER_CLASSES)) return 1;
-  if (t->nclass <= 0 || ncell % t->nclass != 0) {
-    qp::set_error("%s: QP_COLL_MEMBER_CLASSES needs ncell (%lld) to be a multiple of nclass (%d)", who, (long long)ncell,
-                  t->nclass);
-    return 0;
-  }
-  if (!t->cls) {
-    qp::set_error("%s: QP_COLL_MEMBER_CLASSES needs cls (the kernels without member tables read it)", who);
-    return 0;
-  }
-  return 1;
-}
+// ---------------------------------------------------------------------------------------------------------
+// Entry points.  `who` is the exported function the caller used: every message names it.
+// ---------------------------------------------------------------------------------------------------------
+#define QP_REQUIRE_AS(who, cond, msg)         \
+  do {                                        \
+    if (!(cond)) {                            \
+      qp::set_error("%s: %s", who, msg);      \
+      return QP_ERR_INVALID_ARGUMENT;         \
+    }                                         \
+  } while (0)
 
-static int collision_step_impl(const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
-                               const double* state_in, double* state_out, double* phonon, double* ph_scratch,
-                               double dE, double dt, int enable_recombination, int enable_scattering,
-                               int update_phonons, qp::PauliPartial* guard, double guard_floor, bool* guard_done,
-                               void* stream) {
-  if (guard_done) *guard_done = false;
-  QP_REQUIRE(t != nullptr, "tables are NULL");
+// What every collision entry point checks of its tables before it reads further.
+static int validate_tables(const qp_collision_tables* t, int64_t ncell, const char* who) {
+  QP_REQUIRE_AS(who, t != nullptr, "tables are NULL");
   if (t->struct_size != sizeof(qp_collision_tables)) {
-    qp::set_error("qp_collision_step: qp_collision_tables.struct_size is %u, this library expects %zu (binding built against "
-                  "another header revision)", t->struct_size, sizeof(qp_collision_tables));
+    qp::set_error("%s: qp_collision_tables.struct_size is %u, this library expects %zu (binding built against another "
+                  "header revision)", who, t->struct_size, sizeof(qp_collision_tables));
     return QP_ERR_INVALID_ARGUMENT;
   }
-  QP_REQUIRE(t->ne > 0 && t->nw > 0 && t->nclass > 0, "ne, nw, nclass must be positive");
-  QP_REQUIRE(t->rho && t->idx_diff && t->idx_sum && t->sign, "rho / idx maps / sign must be non-NULL");
-  QP_REQUIRE(t->nclass == 1 || t->cls, "cls is required when nclass > 1");
-  QP_REQUIRE(flags && state_in && state_out && phonon, "flags, state_in, state_out, phonon must be non-NULL");
-  QP_REQUIRE(state_in != state_out, "state_in and state_out must not alias");
-  QP_REQUIRE(ncell > 0, "ncell must be positive");
-  if (!member_classes_ok(t, ncell, "qp_collision_step")) return QP_ERR_INVALID_ARGUMENT;
-  const bool member_classes = (t->flags & QP_COLL_MEMBER_CLASSES) && t->nclass > 1;
-  const bool no_scratch_ok = !(t->flags & QP_COLL_FORCE_GENERIC) && t->ne <= 64 && t->nw <= 192;
-  QP_REQUIRE(!(update_phonons && (enable_recombination || enable_scattering)) || ph_scratch || no_scratch_ok,
-             "ph_scratch is required when phonons are updated by the generic kernel");
-  QP_REQUIRE((t->diag_bin == nullptr) == (t->anti_bin == nullptr), "diag_bin and anti_bin come together");
-  // merged bins (QP_COLL_SHARED_BINS): the register kernels park per-diagonal sums in ph_scratch (2 planes per merged bin);
-  // without scratch only the variants that never write phonons qualify
-  const bool shared_ok = !(t->flags & QP_COLL_SHARED_BINS) || ph_scratch ||
-                         !(update_phonons && enable_recombination && enable_scattering && t->kr0 && t->ks0);
-  // 32 <= ne <= 64 with the diagonal-major tables: one launch instead of the three of the split path
-  if (t->diag_bin && t->nclass == 1 && qp::collision_onepass_supported(t->ne) && !(t->flags & (QP_COLL_FORCE_GENERIC | QP_COLL_FORCE_WAVE)) &&
-      shared_ok && ncell < (1L << 28) &&
-      qp::collision_onepass_dispatch(*t, ph_scratch, flags, (long)ncell, state_in, state_out, phonon, dE, dt,
-                                     enable_scattering && t->ks0, enable_recombination && t->kr0,
-                                     update_phonons && ((enable_scattering && t->ks0) || (enable_recombination && t->kr0)),
-                                     (hipStream_t)stream))
-    return qp::check_launch("qp_collision_step(one pass)");
-  if (t->diag_bin && t->nclass == 1 && !(t->flags & (QP_COLL_FORCE_GENERIC | QP_COLL_FORCE_WAVE)) && shared_ok &&
-      qp::collision_fast_dispatch(t->ne, t->kr0, t->ks0, t->rho, t->diag_bin, t->anti_bin, ph_scratch, flags, (long)ncell,
-                                  state_in, state_out, phonon, dE, dt, enable_recombination, enable_scattering,
-                                  update_phonons, guard, guard_floor, guard_done, (hipStream_t)stream))
-    return qp::check_launch("qp_collision_step(fast)");
-  // one table per ensemble member: the register kernels that pick the wave's table (aligned members, ne = 4 ... 16); every
-  // other member-class table runs the one-wave-per-pixel or generic kernel below through `cls`
-  if (member_classes && t->diag_bin && !(t->flags & (QP_COLL_FORCE_GENERIC | QP_COLL_FORCE_WAVE)) && shared_ok &&
-      qp::collision_member_tables_supported(t->ne) &&
-      qp::collision_fast_dispatch_members(t->ne, t->nclass, t->kr0, t->ks0, t->rho, t->diag_bin, t->anti_bin, ph_scratch,
-                                          flags, (long)ncell, state_in, state_out, phonon, dE, dt, enable_recombination,
-                                          enable_scattering, update_phonons, guard, guard_floor, guard_done,
-                                          (hipStream_t)stream))
-    return qp::check_launch("qp_collision_step(fast, member classes)");
-  // gap classes with the separable kernel tables: the one-pass kernel where it exists ...
-  if (t->diag_bin && t->nclass > 1 && !member_classes && qp::collision_onepass_supported(t->ne) &&
-      !(t->flags & (QP_COLL_FORCE_GENERIC | QP_COLL_FORCE_WAVE)) && shared_ok && ncell < (1L << 28) &&
-      qp::collision_onepass_dispatch_classes(*t, ph_scratch, flags, (long)ncell, state_in, state_out, phonon, dE, dt,
-                                             enable_scattering && t->ks0, enable_recombination && t->kr0,
-                                             update_phonons && ((enable_scattering && t->ks0) || (enable_recombination && t->kr0)),
-                                             (hipStream_t)stream))
-    return qp::check_launch("qp_collision_step(one pass, gap classes)");
-  // ... else the register kernels that form K per pixel
-  if (t->diag_bin && t->nclass > 1 && !member_classes && t->gap_sq && t->pair_inv && t->cls &&
-      (!(enable_recombination && t->kr0) || t->kr_amp) && (!(enable_scattering && t->ks0) || t->ks_amp) &&
-      !(t->flags & (QP_COLL_FORCE_GENERIC | QP_COLL_FORCE_WAVE)) && shared_ok &&
-      qp::collision_fast_dispatch_classes(t->ne, t->rho, t->cls, t->gap_sq, enable_recombination ? t->kr_amp : nullptr,
-                                          enable_scattering ? t->ks_amp : nullptr, t->pair_inv, t->diag_bin, t->anti_bin,
-                                          ph_scratch, flags, (long)ncell, state_in, state_out, phonon, dE, dt,
-                                          enable_recombination, enable_scattering, update_phonons, guard, guard_floor,
-                                          guard_done, (hipStream_t)stream))
-    return qp::check_launch("qp_collision_step(fast, gap classes)");
-  // NE <= 64: one wave per pixel (any class map; LDS atomics unless the host vouched for the bin-map structure)
-  if (!(t->flags & QP_COLL_FORCE_GENERIC)) {
-    qp::WaveCollView wv{t->ne, t->nw, t->nclass, t->kr0, t->ks0, t->rho, t->idx_diff, t->idx_sum, t->sign, t->cls,
-                        t->diag_bin, t->anti_bin};
-    if (qp::collision_wave_dispatch(wv, t->diag_bin != nullptr, flags, (long)ncell, state_in, state_out, phonon, dE, dt,
-                                    enable_recombination, enable_scattering, update_phonons, (hipStream_t)stream))
-      return qp::check_launch("qp_collision_step(wave)");
+  QP_REQUIRE_AS(who, ncell > 0 && t->rho != nullptr, "ncell must be positive, rho non-NULL");
+  // QP_COLL_MEMBER_CLASSES: the cells divide evenly among the classes, and the class map of the fallback kernels is there
+  if (t->flags & QP_COLL_MEMBER_CLASSES) {
+    if (t->nclass <= 0 || ncell % t->nclass != 0) {
+      qp::set_error("%s: QP_COLL_MEMBER_CLASSES needs ncell (%lld) to be a multiple of nclass (%d)", who, (long long)ncell,
+                    t->nclass);
+      return QP_ERR_INVALID_ARGUMENT;
+    }
+    QP_REQUIRE_AS(who, t->cls, "QP_COLL_MEMBER_CLASSES needs cls (the kernels without member tables read it)");
   }
-  qp::CollView v{t->ne, t->nw, t->nclass, t->kr0, t->ks0, t->rho, t->idx_diff, t->idx_sum, t->sign, t->cls};
-  const unsigned blocks = (unsigned)((ncell + 255) / 256);
-  hipLaunchKernelGGL(qp::collision_generic_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, v, flags,
-                     (long)ncell, state_in, state_out, phonon, ph_scratch, dE, dt, enable_recombination,
-                     enable_scattering, update_phonons);
-  return qp::check_launch("qp_collision_step");
+  return QP_OK;
+}
+
+// ... and what the single-step family (and the route query) asks on top: all its kernels walk the bin maps
+static int validate_step_tables(const qp_collision_tables* t, int64_t ncell, int en_r, int en_s, int upd, bool have_scratch,
+                                const char* who) {
+  if (const int rc = validate_tables(t, ncell, who)) return rc;
+  QP_REQUIRE_AS(who, t->ne > 0 && t->nw > 0 && t->nclass > 0, "ne, nw, nclass must be positive");
+  QP_REQUIRE_AS(who, t->idx_diff && t->idx_sum && t->sign, "idx maps / sign must be non-NULL");
+  QP_REQUIRE_AS(who, t->nclass == 1 || t->cls, "cls is required when nclass > 1");
+  const bool no_scratch_ok = !(t->flags & QP_COLL_FORCE_GENERIC) && t->ne <= 64 && t->nw <= 192;
+  QP_REQUIRE_AS(who, !(upd && (en_r || en_s)) || have_scratch || no_scratch_ok,
+                "ph_scratch is required when phonons are updated by the generic kernel");
+  QP_REQUIRE_AS(who, (t->diag_bin == nullptr) == (t->anti_bin == nullptr), "diag_bin and anti_bin come together");
+  return QP_OK;
+}
+
+extern "C" int qp_collision_route(const qp_collision_tables* t, int64_t ncell, int enable_recombination,
+                                  int enable_scattering, int update_phonons, int have_scratch) {
+  if (const int rc = validate_step_tables(t, ncell, enable_recombination, enable_scattering, update_phonons,
+                                          have_scratch != 0, "qp_collision_route"))
+    return rc;
+  return qp::collision_route(*t, (long)ncell, enable_recombination, enable_scattering, update_phonons, have_scratch != 0);
+}
+
+// One collision step for the exported function `who`; *route_out (may be NULL) receives the route that ran.
+static int collision_step_impl(const char* who, const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
+                               const double* state_in, double* state_out, double* phonon, double* ph_scratch, double dE,
+                               double dt, int en_r, int en_s, int upd, qp::PauliPartial* guard, double guard_floor,
+                               qp::Route* route_out, void* stream) {
+  if (const int rc = validate_step_tables(t, ncell, en_r, en_s, upd, ph_scratch != nullptr, who)) return rc;
+  QP_REQUIRE_AS(who, flags && state_in && state_out && phonon, "flags, state_in, state_out, phonon must be non-NULL");
+  QP_REQUIRE_AS(who, state_in != state_out, "state_in and state_out must not alias");
+  const qp::Route route = qp::collision_route(*t, (long)ncell, en_r, en_s, upd, ph_scratch != nullptr);
+  if (route_out) *route_out = route;
+  // the gap-class register kernels take their processes from the amplitude tables
+  const bool classes = route == QP_ROUTE_REGISTER_CLASSES;
+  const bool s = en_s && (classes ? t->ks_amp : t->ks0), r = en_r && (classes ? t->kr_amp : t->kr0);
+  const qp::CollCall c{flags, (long)ncell, state_in, state_out, phonon, ph_scratch, dE, dt, 0.0, 0.0, s, r, upd && (s || r),
+                       guard, guard_floor, (hipStream_t)stream};
+  switch (route) {
+    case QP_ROUTE_ONEPASS:
+    case QP_ROUTE_ONEPASS_CLASSES:
+      qp::collision_onepass_dispatch(route, *t, c);
+      break;
+    case QP_ROUTE_REGISTER:
+    case QP_ROUTE_REGISTER_MEMBERS:
+    case QP_ROUTE_REGISTER_CLASSES:
+    case QP_ROUTE_COPY:
+      qp::collision_fast_dispatch(route, *t, c);
+      break;
+    case QP_ROUTE_WAVE: {
+      const qp::WaveCollView wv{t->ne, t->nw, t->nclass, t->kr0, t->ks0, t->rho, t->idx_diff, t->idx_sum, t->sign, t->cls,
+                                t->diag_bin, t->anti_bin};
+      qp::collision_wave_dispatch(wv, t->diag_bin != nullptr, c);
+      break;
+    }
+    case QP_ROUTE_GENERIC: {    // the kernel tests the caller's switches itself (it also rewrites phonons with no table)
+      const qp::CollView v{t->ne, t->nw, t->nclass, t->kr0, t->ks0, t->rho, t->idx_diff, t->idx_sum, t->sign, t->cls};
+      hipLaunchKernelGGL(qp::collision_generic_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0,
+                         (hipStream_t)stream, v, flags, (long)ncell, state_in, state_out, phonon, ph_scratch, dE, dt, en_r,
+                         en_s, upd);
+      break;
+    }
+  }
+  return qp::check_launch(who);
 }
 
 extern "C" int qp_collision_step(const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
                                  const double* state_in, double* state_out, double* phonon, double* ph_scratch,
                                  double dE, double dt, int enable_recombination, int enable_scattering,
                                  int update_phonons, void* stream) {
-  return collision_step_impl(t, flags, ncell, state_in, state_out, phonon, ph_scratch, dE, dt, enable_recombination,
-                             enable_scattering, update_phonons, nullptr, 0.0, nullptr, stream);
+  return collision_step_impl("qp_collision_step", t, flags, ncell, state_in, state_out, phonon, ph_scratch, dE, dt,
+                             enable_recombination, enable_scattering, update_phonons, nullptr, 0.0, nullptr, stream);
 }
 
 extern "C" int64_t qp_collision_guard_workspace_bytes(int64_t ncell) {
@@ -291,28 +297,6 @@ extern "C" int64_t qp_collision_guard_workspace_bytes(int64_t ncell) {
   const int64_t fused = waves * (int64_t)sizeof(qp::PauliPartial);
   const int64_t plain = qp_pauli_workspace_bytes();
   return fused > plain ? fused : plain;
-}
-
-extern "C" int qp_collision_step_guarded(const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
-                                         const double* state_in, double* state_out, double* phonon, double* ph_scratch,
-                                         double dE, double dt, int enable_recombination, int enable_scattering,
-                                         int update_phonons, double density_floor, void* guard_workspace,
-                                         double* out_vals, int64_t* out_idx, void* stream) {
-  QP_REQUIRE(guard_workspace && out_vals && out_idx, "guard_workspace, out_vals, out_idx must be non-NULL");
-  auto* parts = (qp::PauliPartial*)guard_workspace;
-  bool done = false;
-  const int rc = collision_step_impl(t, flags, ncell, state_in, state_out, phonon, ph_scratch, dE, dt, enable_recombination,
-                                     enable_scattering, update_phonons, parts + qp::kGuardMergeBlocks, density_floor, &done,
-                                     stream);
-  if (rc != QP_OK) return rc;
-  if (done) {      // one partial per wave of the register kernel (128-thread blocks): finish the reduction
-    const long nparts = ((long)ncell + 127) / 128 * 2;
-    qp::pauli_finish(parts + qp::kGuardMergeBlocks, nparts, parts, out_vals, (long*)out_idx, (hipStream_t)stream);
-    return qp::check_launch("qp_collision_step_guarded");
-  }
-  // kernels without the fused epilogue (split kernels of NE >= 32, wave and generic kernels): separate pass
-  return qp_pauli_stats(state_out, t->rho, t->cls, flags, t->ne, t->nclass, ncell, density_floor, guard_workspace,
-                        out_vals, out_idx, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -371,55 +355,104 @@ extern "C" int qp_collision_register_kernel_available(int32_t ne) { return qp::c
 
 extern "C" int qp_collision_pair_available(int32_t ne) { return qp::collision_pair_supported(ne); }
 
-extern "C" int qp_collision_double_step_guarded(const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
-                                                const double* state_in, double* state_out, double* phonon, double dE,
-                                                double dt_first, double dt_second, double gen_amount,
-                                                int enable_recombination, int enable_scattering, int update_phonons,
-                                                double density_floor, void* guard_workspace, double* out_vals,
-                                                int64_t* out_idx, void* stream) {
-  QP_REQUIRE(t != nullptr, "tables are NULL");
-  if (t->struct_size != sizeof(qp_collision_tables)) {
-    qp::set_error("qp_collision_double_step_guarded: qp_collision_tables.struct_size is %u, this library expects %zu",
-                  t->struct_size, sizeof(qp_collision_tables));
-    return QP_ERR_INVALID_ARGUMENT;
-  }
-  QP_REQUIRE(flags && state_in && state_out && phonon && state_in != state_out, "flags, state_in, state_out (distinct), phonon");
-  QP_REQUIRE(guard_workspace && out_vals && out_idx, "guard_workspace, out_vals, out_idx must be non-NULL");
-  QP_REQUIRE(ncell > 0 && t->rho != nullptr, "ncell must be positive, rho non-NULL");
-  if (!member_classes_ok(t, ncell, "qp_collision_double_step_guarded")) return QP_ERR_INVALID_ARGUMENT;
-  const bool s = enable_scattering && t->ks0, r = enable_recombination && t->kr0;
-  auto* parts = (qp::PauliPartial*)guard_workspace;
-  if (!qp::collision_pair_dispatch(*t, flags, (long)ncell, state_in, state_out, phonon, dE, dt_first, dt_second, gen_amount, s, r,
-                                   update_phonons && (s || r), parts + qp::kGuardMergeBlocks, density_floor,
-                                   (hipStream_t)stream)) {
-    qp::set_error("qp_collision_double_step_guarded: no fused double half-step kernel for these tables (ne = %d)", t->ne);
-    return QP_ERR_UNSUPPORTED;
-  }
-  const long nparts = ((long)ncell + 127) / 128 * 2;
-  qp::pauli_finish(parts + qp::kGuardMergeBlocks, nparts, parts, out_vals, (long*)out_idx, (hipStream_t)stream);
-  return qp::check_launch("qp_collision_double_step_guarded");
-}
-
 // 1 when the single-pass and double half-step register kernels exist in their member-table form (QP_COLL_MEMBER_CLASSES)
 extern "C" int qp_collision_member_tables_available(int32_t ne) { return qp::collision_member_tables_supported(ne); }
 
 extern "C" int qp_collision_onepass_available(int32_t ne) { return qp::collision_onepass_supported(ne); }
 
-// 2nd bit: the gap-class variant (separable kernel tables, qp_collision_tables::gap_sq ...) exists as well
+// 1 when the gap-class variant (separable kernel tables, qp_collision_tables::gap_sq ...) exists as well
 extern "C" int qp_collision_register_kernel_classes(int32_t ne) { return qp::collision_fast_classes_supported(ne); }
 
 // ---------------------------------------------------------------------------------------------------------
-// Ensembles: the guarded calls with the Pauli guard reduced per member (qp_pauli_stats_members semantics).  The register
-// and pair kernels write one partial per wave of 64 consecutive pixels; with ncell_member % 64 == 0 no wave straddles two
-// members, so one finishing block per member groups them (64 w / ncell_member) without another pass over the state.
+// The guarded calls.  The register and pair kernels write one guard partial per wave of 64 consecutive pixels.  The plain
+// calls reduce them all (pauli_finish).  The ensemble calls (`per_member`) reduce them per member (qp_pauli_stats_members
+// semantics): with ncell_member % 64 == 0 no wave straddles two members, so one finishing block per member groups them
+// (64 w / ncell_member) without another pass over the state.  The plain call is the case of one member that owns all cells.
 // ---------------------------------------------------------------------------------------------------------
-static int members_args_ok(int64_t ncell, int64_t ncell_member, int64_t members, const char* who) {
-  if (ncell_member <= 0 || members <= 0 || ncell_member * members != ncell) {
+struct GuardOut {
+  void* workspace;
+  bool per_member;
+  int64_t ncell_member, members;
+  double* vals;
+  int64_t* idx;
+};
+
+static int guard_out_ok(const GuardOut& g, int64_t ncell, const char* who) {
+  QP_REQUIRE_AS(who, g.workspace && g.vals && g.idx, "guard_workspace, out_vals, out_idx must be non-NULL");
+  if (g.per_member && (g.ncell_member <= 0 || g.members <= 0 || g.ncell_member * g.members != ncell)) {
     qp::set_error("%s: ncell (%lld) must equal ncell_member (%lld) * members (%lld)", who, (long long)ncell,
-                  (long long)ncell_member, (long long)members);
-    return 0;
+                  (long long)g.ncell_member, (long long)g.members);
+    return QP_ERR_INVALID_ARGUMENT;
   }
-  return 1;
+  return QP_OK;
+}
+
+// finishes the reduction of the per-wave partials the collision kernel of this call has written (128-thread blocks)
+static int guard_finish(const GuardOut& g, int64_t ncell, const char* who, void* stream) {
+  auto* parts = (qp::PauliPartial*)g.workspace;
+  if (g.per_member)
+    qp::pauli_finish_members(parts + qp::kGuardMergeBlocks, (long)g.ncell_member, (long)g.members, g.vals, (long*)g.idx,
+                             (hipStream_t)stream);
+  else
+    qp::pauli_finish(parts + qp::kGuardMergeBlocks, ((long)ncell + 127) / 128 * 2, parts, g.vals, (long*)g.idx,
+                     (hipStream_t)stream);
+  return qp::check_launch(who);
+}
+
+static int step_guarded_impl(const char* who, const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
+                             const double* state_in, double* state_out, double* phonon, double* ph_scratch, double dE,
+                             double dt, int en_r, int en_s, int upd, double density_floor, const GuardOut& g, void* stream) {
+  if (const int rc = guard_out_ok(g, ncell, who)) return rc;
+  // a wave's partial belongs to one member only when the members are wave-aligned
+  const bool aligned = !g.per_member || g.ncell_member % 64 == 0;
+  qp::PauliPartial* const parts = aligned ? (qp::PauliPartial*)g.workspace + qp::kGuardMergeBlocks : nullptr;
+  qp::Route route;
+  if (const int rc = collision_step_impl(who, t, flags, ncell, state_in, state_out, phonon, ph_scratch, dE, dt, en_r, en_s,
+                                         upd, parts, density_floor, &route, stream))
+    return rc;
+  if (parts && qp::route_writes_guard(route, t->ne)) return guard_finish(g, ncell, who, stream);
+  // kernels without the fused epilogue (split kernels of NE >= 32, one-pass, copy, wave and generic kernels): separate pass
+  if (g.per_member)
+    return qp_pauli_stats_members(state_out, t->rho, t->cls, flags, t->ne, t->nclass, g.ncell_member, g.members,
+                                  density_floor, g.workspace, g.vals, g.idx, stream);
+  return qp_pauli_stats(state_out, t->rho, t->cls, flags, t->ne, t->nclass, ncell, density_floor, g.workspace, g.vals, g.idx,
+                        stream);
+}
+
+static int double_step_guarded_impl(const char* who, const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
+                                    const double* state_in, double* state_out, double* phonon, double dE, double dt_first,
+                                    double dt_second, double gen_amount, int en_r, int en_s, int upd, double density_floor,
+                                    const GuardOut& g, void* stream) {
+  if (const int rc = validate_tables(t, ncell, who)) return rc;
+  QP_REQUIRE_AS(who, flags && state_in && state_out && phonon && state_in != state_out,
+                "flags, state_in, state_out (distinct), phonon");
+  if (const int rc = guard_out_ok(g, ncell, who)) return rc;
+  if (g.per_member && g.ncell_member % 64 != 0) {
+    qp::set_error("%s: ncell_member (%lld) is not a multiple of 64", who, (long long)g.ncell_member);
+    return QP_ERR_UNSUPPORTED;
+  }
+  const bool s = en_s && t->ks0, r = en_r && t->kr0;
+  const qp::PairRoute route = qp::collision_pair_route(*t, (long)ncell, s, r);
+  if (route == qp::PairRoute::None) {
+    qp::set_error("%s: no fused double half-step kernel for these tables (ne = %d, ncell = %lld)", who, t->ne,
+                  (long long)ncell);
+    return QP_ERR_UNSUPPORTED;
+  }
+  const qp::CollCall c{flags, (long)ncell, state_in, state_out, phonon, nullptr, dE, dt_first, dt_second, gen_amount, s, r,
+                       upd && (s || r), (qp::PauliPartial*)g.workspace + qp::kGuardMergeBlocks, density_floor,
+                       (hipStream_t)stream};
+  qp::collision_pair_dispatch(route, *t, c);
+  return guard_finish(g, ncell, who, stream);
+}
+
+extern "C" int qp_collision_step_guarded(const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
+                                         const double* state_in, double* state_out, double* phonon, double* ph_scratch,
+                                         double dE, double dt, int enable_recombination, int enable_scattering,
+                                         int update_phonons, double density_floor, void* guard_workspace,
+                                         double* out_vals, int64_t* out_idx, void* stream) {
+  return step_guarded_impl("qp_collision_step_guarded", t, flags, ncell, state_in, state_out, phonon, ph_scratch, dE, dt,
+                           enable_recombination, enable_scattering, update_phonons, density_floor,
+                           {guard_workspace, false, ncell, 1, out_vals, out_idx}, stream);
 }
 
 extern "C" int qp_collision_step_guarded_members(const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
@@ -428,22 +461,20 @@ extern "C" int qp_collision_step_guarded_members(const qp_collision_tables* t, c
                                                  int enable_scattering, int update_phonons, double density_floor,
                                                  void* guard_workspace, int64_t ncell_member, int64_t members,
                                                  double* out_vals, int64_t* out_idx, void* stream) {
-  QP_REQUIRE(guard_workspace && out_vals && out_idx, "guard_workspace, out_vals, out_idx must be non-NULL");
-  if (!members_args_ok(ncell, ncell_member, members, "qp_collision_step_guarded_members")) return QP_ERR_INVALID_ARGUMENT;
-  auto* parts = (qp::PauliPartial*)guard_workspace;
-  const bool aligned = ncell_member % 64 == 0;
-  bool done = false;
-  const int rc = collision_step_impl(t, flags, ncell, state_in, state_out, phonon, ph_scratch, dE, dt, enable_recombination,
-                                     enable_scattering, update_phonons, aligned ? parts + qp::kGuardMergeBlocks : nullptr,
-                                     density_floor, aligned ? &done : nullptr, stream);
-  if (rc != QP_OK) return rc;
-  if (done) {
-    qp::pauli_finish_members(parts + qp::kGuardMergeBlocks, (long)ncell_member, (long)members, out_vals, (long*)out_idx,
-                             (hipStream_t)stream);
-    return qp::check_launch("qp_collision_step_guarded_members");
-  }
-  return qp_pauli_stats_members(state_out, t->rho, t->cls, flags, t->ne, t->nclass, ncell_member, members, density_floor,
-                                guard_workspace, out_vals, out_idx, stream);
+  return step_guarded_impl("qp_collision_step_guarded_members", t, flags, ncell, state_in, state_out, phonon, ph_scratch, dE,
+                           dt, enable_recombination, enable_scattering, update_phonons, density_floor,
+                           {guard_workspace, true, ncell_member, members, out_vals, out_idx}, stream);
+}
+
+extern "C" int qp_collision_double_step_guarded(const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
+                                                const double* state_in, double* state_out, double* phonon, double dE,
+                                                double dt_first, double dt_second, double gen_amount,
+                                                int enable_recombination, int enable_scattering, int update_phonons,
+                                                double density_floor, void* guard_workspace, double* out_vals,
+                                                int64_t* out_idx, void* stream) {
+  return double_step_guarded_impl("qp_collision_double_step_guarded", t, flags, ncell, state_in, state_out, phonon, dE,
+                                  dt_first, dt_second, gen_amount, enable_recombination, enable_scattering, update_phonons,
+                                  density_floor, {guard_workspace, false, ncell, 1, out_vals, out_idx}, stream);
 }
 
 extern "C" int qp_collision_double_step_guarded_members(const qp_collision_tables* t, const uint8_t* flags, int64_t ncell,
@@ -452,32 +483,8 @@ extern "C" int qp_collision_double_step_guarded_members(const qp_collision_table
                                                         int enable_recombination, int enable_scattering, int update_phonons,
                                                         double density_floor, void* guard_workspace, int64_t ncell_member,
                                                         int64_t members, double* out_vals, int64_t* out_idx, void* stream) {
-  QP_REQUIRE(t != nullptr, "tables are NULL");
-  if (t->struct_size != sizeof(qp_collision_tables)) {
-    qp::set_error("qp_collision_double_step_guarded_members: qp_collision_tables.struct_size is %u, this library expects %zu",
-                  t->struct_size, sizeof(qp_collision_tables));
-    return QP_ERR_INVALID_ARGUMENT;
-  }
-  QP_REQUIRE(flags && state_in && state_out && phonon && state_in != state_out, "flags, state_in, state_out (distinct), phonon");
-  QP_REQUIRE(guard_workspace && out_vals && out_idx, "guard_workspace, out_vals, out_idx must be non-NULL");
-  QP_REQUIRE(ncell > 0 && t->rho != nullptr, "ncell must be positive, rho non-NULL");
-  if (!members_args_ok(ncell, ncell_member, members, "qp_collision_double_step_guarded_members")) return QP_ERR_INVALID_ARGUMENT;
-  if (!member_classes_ok(t, ncell, "qp_collision_double_step_guarded_members")) return QP_ERR_INVALID_ARGUMENT;
-  if (ncell_member % 64 != 0) {
-    qp::set_error("qp_collision_double_step_guarded_members: ncell_member (%lld) is not a multiple of 64",
-                  (long long)ncell_member);
-    return QP_ERR_UNSUPPORTED;
-  }
-  const bool s = enable_scattering && t->ks0, r = enable_recombination && t->kr0;
-  auto* parts = (qp::PauliPartial*)guard_workspace;
-  if (!qp::collision_pair_dispatch(*t, flags, (long)ncell, state_in, state_out, phonon, dE, dt_first, dt_second, gen_amount, s, r,
-                                   update_phonons && (s || r), parts + qp::kGuardMergeBlocks, density_floor,
-                                   (hipStream_t)stream)) {
-    qp::set_error("qp_collision_double_step_guarded_members: no fused double half-step kernel for these tables "
-                  "(ne = %d, ncell = %lld)", t->ne, (long long)ncell);
-    return QP_ERR_UNSUPPORTED;
-  }
-  qp::pauli_finish_members(parts + qp::kGuardMergeBlocks, (long)ncell_member, (long)members, out_vals, (long*)out_idx,
-                           (hipStream_t)stream);
-  return qp::check_launch("qp_collision_double_step_guarded_members");
+  return double_step_guarded_impl("qp_collision_double_step_guarded_members", t, flags, ncell, state_in, state_out, phonon,
+                                  dE, dt_first, dt_second, gen_amount, enable_recombination, enable_scattering,
+                                  update_phonons, density_floor,
+                                  {guard_workspace, true, ncell_member, members, out_vals, out_idx}, stream);
 }

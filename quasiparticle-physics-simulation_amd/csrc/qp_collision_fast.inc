@@ -10,7 +10,7 @@
 // no indexed register arrays (everything is unrolled at compile time), tables arrive as scalar loads.
 // K^s_0 and K^r_0 are symmetric, so each unordered pair is visited once.
 #pragma once
-#include "qp_common.h"
+#include "qp_collision_dispatch.h"
 
 namespace qp {
 
@@ -278,7 +278,7 @@ collision_diag_kernel(typename coll_view<MEMB>::type t, const uint8_t* __restric
 #endif
   constexpr int PF = UPD ? QP_PF_UPD : 4;
 
-  // (NE >= 32 never gets here: launch_one splits it into collision_range_kernel passes + collision_phonon_kernel.)
+  // (NE >= 32 never gets here: launch_register splits it into collision_range_kernel passes + collision_phonon_kernel.)
   double n[NE], q[NE], ga[NE], la[NE];
 #pragma unroll
   for (int i = 0; i < NE; ++i) {
@@ -623,110 +623,39 @@ __global__ void __launch_bounds__(128) collision_range_kernel(CollFastView t, co
 #undef QP_IN
 }
 
-template <int NE, bool S, bool R, bool U>
-static void launch_one(const CollFastView& v, const uint8_t* flags, long ncell, const double* sin_, double* sout,
-                       double* ph, double dE, double dt, hipStream_t stream) {
-  const unsigned blocks = (unsigned)((ncell + 127) / 128);
-  if constexpr (NE >= 32) {   // split: quasiparticle half in two target ranges (old P), then the phonon half (old n, old P)
+// The launches of one (NE, S, R) of the register family: NE >= 32 as the split - the quasiparticle half in two target ranges
+// (old P), then the phonon half (old n, old P) when phonons are dynamic - smaller NE as the single-pass kernel.  PARAM: the
+// gap-class form of every kernel (q resident, K from the amplitude tables).  MEMB: member tables, single-pass sizes only.
+// The kernels without MEMB are launched with the CollFastView part of the view, which is their whole argument.
+template <int NE, bool S, bool R, bool PARAM, bool MEMB>
+static void launch_register(const CollFastViewM& vm, const CollCall& c) {
+  static_assert(!MEMB || NE < 32, "the split kernels have no member-table form");
+  const typename coll_view<MEMB>::type& v = vm;
+  const unsigned blocks = (unsigned)((c.ncell + 127) / 128);
+  if constexpr (NE >= 32) {
     constexpr int MID = NE / 2;
-    hipLaunchKernelGGL((collision_range_kernel<NE, S, R, 0, MID>), dim3(blocks), dim3(128), 0, stream, v, flags, ncell,
-                       sin_, sout, (const double*)ph, dE, dt);
-    hipLaunchKernelGGL((collision_range_kernel<NE, S, R, MID, NE>), dim3(blocks), dim3(128), 0, stream, v, flags, ncell,
-                       sin_, sout, (const double*)ph, dE, dt);
-    if (U)
-      hipLaunchKernelGGL((collision_phonon_kernel<NE, S, R>), dim3(blocks), dim3(128), 0, stream, v, flags, ncell, sin_, ph,
-                         dE, dt);
+    hipLaunchKernelGGL((collision_range_kernel<NE, S, R, 0, MID, PARAM>), dim3(blocks), dim3(128), 0, c.stream, v, c.flags,
+                       c.ncell, c.sin, c.sout, (const double*)c.ph, c.dE, c.dt);
+    hipLaunchKernelGGL((collision_range_kernel<NE, S, R, MID, NE, PARAM>), dim3(blocks), dim3(128), 0, c.stream, v, c.flags,
+                       c.ncell, c.sin, c.sout, (const double*)c.ph, c.dE, c.dt);
+    if (c.u)
+      hipLaunchKernelGGL((collision_phonon_kernel<NE, S, R, PARAM>), dim3(blocks), dim3(128), 0, c.stream, v, c.flags,
+                         c.ncell, c.sin, c.ph, c.dE, c.dt);
+  } else if (c.u) {
+    hipLaunchKernelGGL((collision_diag_kernel<NE, S, R, true, PARAM, MEMB>), dim3(blocks), dim3(128), 0, c.stream, v,
+                       c.flags, c.ncell, c.sin, c.sout, c.ph, c.dE, c.dt);
   } else {
-    hipLaunchKernelGGL((collision_diag_kernel<NE, S, R, U>), dim3(blocks), dim3(128), 0, stream, v, flags, ncell, sin_,
-                       sout, ph, dE, dt);
+    hipLaunchKernelGGL((collision_diag_kernel<NE, S, R, false, PARAM, MEMB>), dim3(blocks), dim3(128), 0, c.stream, v,
+                       c.flags, c.ncell, c.sin, c.sout, c.ph, c.dE, c.dt);
   }
 }
 
-// One (NE, S, R) combination: frozen and dynamic phonons.
+// the launcher families of the register kernels (qp_collision_dispatch.h): one gap class, gap classes, member tables
 template <int NE, bool S, bool R>
-static void launch_sr(const CollFastView& v, const uint8_t* flags, long ncell, const double* sin_, double* sout, double* ph,
-                      double dE, double dt, bool u, hipStream_t stream) {
-  if (u) launch_one<NE, S, R, true>(v, flags, ncell, sin_, sout, ph, dE, dt, stream);
-  else launch_one<NE, S, R, false>(v, flags, ncell, sin_, sout, ph, dE, dt, stream);
-}
-
-// Gap-class variant (collision_diag_kernel<..., PARAM>): single-pass sizes only.
+static void launch_diag(const CollFastViewM& v, const CollCall& c) { launch_register<NE, S, R, false, false>(v, c); }
 template <int NE, bool S, bool R>
-static void launch_srp(const CollFastView& v, const uint8_t* flags, long ncell, const double* sin_, double* sout, double* ph,
-                       double dE, double dt, bool u, hipStream_t stream) {
-  const unsigned blocks = (unsigned)((ncell + 127) / 128);
-  if constexpr (NE >= 32) {   // split as in launch_one, every kernel in its gap-class form (q resident, K from amplitudes)
-    constexpr int MID = NE / 2;
-    hipLaunchKernelGGL((collision_range_kernel<NE, S, R, 0, MID, true>), dim3(blocks), dim3(128), 0, stream, v, flags,
-                       ncell, sin_, sout, (const double*)ph, dE, dt);
-    hipLaunchKernelGGL((collision_range_kernel<NE, S, R, MID, NE, true>), dim3(blocks), dim3(128), 0, stream, v, flags,
-                       ncell, sin_, sout, (const double*)ph, dE, dt);
-    if (u)
-      hipLaunchKernelGGL((collision_phonon_kernel<NE, S, R, true>), dim3(blocks), dim3(128), 0, stream, v, flags, ncell,
-                         sin_, ph, dE, dt);
-  } else if (u) {
-    hipLaunchKernelGGL((collision_diag_kernel<NE, S, R, true, true>), dim3(blocks), dim3(128), 0, stream, v, flags, ncell,
-                       sin_, sout, ph, dE, dt);
-  } else {
-    hipLaunchKernelGGL((collision_diag_kernel<NE, S, R, false, true>), dim3(blocks), dim3(128), 0, stream, v, flags, ncell,
-                       sin_, sout, ph, dE, dt);
-  }
-}
-
-#define QP_DEFINE_DIAGP_SR(N, S, R)                                                                                      \
-  void diag_launcherp_##N##_##S##R(const CollFastView& v, const uint8_t* flags, long ncell, const double* sin_,         \
-                                   double* sout, double* ph, double dE, double dt, bool u, hipStream_t stream) {         \
-    launch_srp<N, S != 0, R != 0>(v, flags, ncell, sin_, sout, ph, dE, dt, u, stream);                                   \
-  }
-#define QP_DEFINE_DIAGP(N) QP_DEFINE_DIAGP_SR(N, 1, 1) QP_DEFINE_DIAGP_SR(N, 0, 1) QP_DEFINE_DIAGP_SR(N, 1, 0)
-
-// Member-class variant (collision_diag_kernel<..., false, true>): the sizes of the double half-step kernel, NE <= 16.
+static void launch_diagp(const CollFastViewM& v, const CollCall& c) { launch_register<NE, S, R, true, false>(v, c); }
 template <int NE, bool S, bool R>
-static void launch_srm(const CollFastViewM& v, const uint8_t* flags, long ncell, const double* sin_, double* sout, double* ph,
-                       double dE, double dt, bool u, hipStream_t stream) {
-  const unsigned blocks = (unsigned)((ncell + 127) / 128);
-  if (u)
-    hipLaunchKernelGGL((collision_diag_kernel<NE, S, R, true, false, true>), dim3(blocks), dim3(128), 0, stream, v, flags,
-                       ncell, sin_, sout, ph, dE, dt);
-  else
-    hipLaunchKernelGGL((collision_diag_kernel<NE, S, R, false, false, true>), dim3(blocks), dim3(128), 0, stream, v, flags,
-                       ncell, sin_, sout, ph, dE, dt);
-}
-
-#define QP_DEFINE_DIAGM_SR(N, S, R)                                                                                      \
-  void diag_launcherm_##N##_##S##R(const CollFastViewM& v, const uint8_t* flags, long ncell, const double* sin_,         \
-                                   double* sout, double* ph, double dE, double dt, bool u, hipStream_t stream) {         \
-    launch_srm<N, S != 0, R != 0>(v, flags, ncell, sin_, sout, ph, dE, dt, u, stream);                                   \
-  }
-#define QP_DEFINE_DIAGM(N) QP_DEFINE_DIAGM_SR(N, 1, 1) QP_DEFINE_DIAGM_SR(N, 0, 1) QP_DEFINE_DIAGM_SR(N, 1, 0)
-#define QP_DECLARE_DIAGM(N)                                                                                               \
-  void diag_launcherm_##N##_11(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,\
-                               bool, hipStream_t);                                                                         \
-  void diag_launcherm_##N##_01(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,\
-                               bool, hipStream_t);                                                                         \
-  void diag_launcherm_##N##_10(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,\
-                               bool, hipStream_t);
-// the NE with a member-class instantiation (single-pass and double half-step kernel alike)
-#define QP_MEMBER_NE_LIST(X) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
-
-typedef void (*diag_launcherm_t)(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,
-                                 bool, hipStream_t);
-typedef void (*diag_launcher_t)(const CollFastView&, const uint8_t*, long, const double*, double*, double*, double, double,
-                                bool, hipStream_t);
-
-// Defines qp::diag_launcher_<N>_<S><R>: the entry the dispatcher in qp_collision_fast.hip looks up.
-#define QP_DEFINE_DIAG_SR(N, S, R)                                                                                       \
-  void diag_launcher_##N##_##S##R(const CollFastView& v, const uint8_t* flags, long ncell, const double* sin_,          \
-                                  double* sout, double* ph, double dE, double dt, bool u, hipStream_t stream) {          \
-    launch_sr<N, S != 0, R != 0>(v, flags, ncell, sin_, sout, ph, dE, dt, u, stream);                                    \
-  }
-#define QP_DEFINE_DIAG(N) QP_DEFINE_DIAG_SR(N, 1, 1) QP_DEFINE_DIAG_SR(N, 0, 1) QP_DEFINE_DIAG_SR(N, 1, 0)
-#define QP_DECLARE_DIAG(N)                                                                                               \
-  void diag_launcher_##N##_11(const CollFastView&, const uint8_t*, long, const double*, double*, double*, double, double, \
-                              bool, hipStream_t);                                                                         \
-  void diag_launcher_##N##_01(const CollFastView&, const uint8_t*, long, const double*, double*, double*, double, double, \
-                              bool, hipStream_t);                                                                         \
-  void diag_launcher_##N##_10(const CollFastView&, const uint8_t*, long, const double*, double*, double*, double, double, \
-                              bool, hipStream_t);
+static void launch_diagm(const CollFastViewM& v, const CollCall& c) { launch_register<NE, S, R, false, true>(v, c); }
 
 }  // namespace qp

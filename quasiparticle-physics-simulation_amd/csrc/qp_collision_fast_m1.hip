@@ -2,12 +2,12 @@
 #include "qp_collision_fast.inc"
 
 namespace qp {
-QP_DEFINE_DIAGM(4)
-QP_DEFINE_DIAGM(5)
-QP_DEFINE_DIAGM(6)
-QP_DEFINE_DIAGM(7)
-QP_DEFINE_DIAGM(8)
-QP_DEFINE_DIAGM(9)
-QP_DEFINE_DIAGM(10)
-QP_DEFINE_DIAGM(11)
+QP_DEFINE_LAUNCHERS(4, diagm)
+QP_DEFINE_LAUNCHERS(5, diagm)
+QP_DEFINE_LAUNCHERS(6, diagm)
+QP_DEFINE_LAUNCHERS(7, diagm)
+QP_DEFINE_LAUNCHERS(8, diagm)
+QP_DEFINE_LAUNCHERS(9, diagm)
+QP_DEFINE_LAUNCHERS(10, diagm)
+QP_DEFINE_LAUNCHERS(11, diagm)
 }  // namespace qp

@@ -2,7 +2,7 @@
 #include "qp_collision_fast.inc"
 
 namespace qp {
-QP_DEFINE_DIAGM(12)
-QP_DEFINE_DIAGM(13)
-QP_DEFINE_DIAGM(14)
+QP_DEFINE_LAUNCHERS(12, diagm)
+QP_DEFINE_LAUNCHERS(13, diagm)
+QP_DEFINE_LAUNCHERS(14, diagm)
 }  // namespace qp

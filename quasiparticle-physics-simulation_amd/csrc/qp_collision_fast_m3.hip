@@ -2,6 +2,6 @@
 #include "qp_collision_fast.inc"
 
 namespace qp {
-QP_DEFINE_DIAGM(15)
-QP_DEFINE_DIAGM(16)
+QP_DEFINE_LAUNCHERS(15, diagm)
+QP_DEFINE_LAUNCHERS(16, diagm)
 }  // namespace qp

@@ -2,6 +2,6 @@
 #include "qp_collision_fast.inc"
 
 namespace qp {
-QP_DEFINE_DIAGP_SR(50, 0, 1)
-QP_DEFINE_DIAGP_SR(50, 1, 0)
+QP_DEFINE_LAUNCHER(50, diagp, 0, 1)
+QP_DEFINE_LAUNCHER(50, diagp, 1, 0)
 }  // namespace qp

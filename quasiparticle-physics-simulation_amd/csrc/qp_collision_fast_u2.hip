@@ -2,8 +2,8 @@
 #include "qp_collision_fast.inc"
 
 namespace qp {
-QP_DEFINE_DIAG(18)
-QP_DEFINE_DIAG(20)
-QP_DEFINE_DIAGP(18)
-QP_DEFINE_DIAGP(20)
+QP_DEFINE_LAUNCHERS(18, diag)
+QP_DEFINE_LAUNCHERS(20, diag)
+QP_DEFINE_LAUNCHERS(18, diagp)
+QP_DEFINE_LAUNCHERS(20, diagp)
 }  // namespace qp

@@ -2,6 +2,6 @@
 #include "qp_collision_fast.inc"
 
 namespace qp {
-QP_DEFINE_DIAG(24)
-QP_DEFINE_DIAGP(24)
+QP_DEFINE_LAUNCHERS(24, diag)
+QP_DEFINE_LAUNCHERS(24, diagp)
 }  // namespace qp

@@ -2,8 +2,8 @@
 #include "qp_collision_fast.inc"
 
 namespace qp {
-QP_DEFINE_DIAG(30)
-QP_DEFINE_DIAG(32)
-QP_DEFINE_DIAGP(30)
-QP_DEFINE_DIAGP(32)
+QP_DEFINE_LAUNCHERS(30, diag)
+QP_DEFINE_LAUNCHERS(32, diag)
+QP_DEFINE_LAUNCHERS(30, diagp)
+QP_DEFINE_LAUNCHERS(32, diagp)
 }  // namespace qp

@@ -2,6 +2,6 @@
 #include "qp_collision_fast.inc"
 
 namespace qp {
-QP_DEFINE_DIAG(40)
-QP_DEFINE_DIAGP(40)
+QP_DEFINE_LAUNCHERS(40, diag)
+QP_DEFINE_LAUNCHERS(40, diagp)
 }  // namespace qp

@@ -2,5 +2,5 @@
 #include "qp_collision_fast.inc"
 
 namespace qp {
-QP_DEFINE_DIAG_SR(50, 1, 1)
+QP_DEFINE_LAUNCHER(50, diag, 1, 1)
 }  // namespace qp

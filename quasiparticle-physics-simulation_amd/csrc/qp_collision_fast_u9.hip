@@ -2,6 +2,6 @@
 #include "qp_collision_fast.inc"
 
 namespace qp {
-QP_DEFINE_DIAG_SR(50, 0, 1)
-QP_DEFINE_DIAG_SR(50, 1, 0)
+QP_DEFINE_LAUNCHER(50, diag, 0, 1)
+QP_DEFINE_LAUNCHER(50, diag, 1, 0)
 }  // namespace qp

@@ -1,73 +1,38 @@
 // Dispatcher of the one-pass collision kernels (qp_collision_onepass.inc); the instantiations live in
 // qp_collision_onepass_u*.hip, one (NE, process combination) per unit so that the build parallelises.
-#include <stdlib.h>
+#include <assert.h>
 
 #include "qp_collision_onepass.inc"
 
 namespace qp {
 
-QP_DECLARE_ONEPASS(50)
-QP_DECLARE_ONEPASS(40)
-QP_DECLARE_ONEPASS(32)
-QP_DECLARE_ONEPASS(30)
-QP_DECLARE_ONEPASS_CLASSES(50, 1, 1)
-QP_DECLARE_ONEPASS_CLASSES(50, 0, 1)
-QP_DECLARE_ONEPASS_CLASSES(50, 1, 0)
+QP_ONEPASS_NE_LIST(QP_DECLARE_LAUNCHERS, onepass)
+QP_ONEPASS_CLASSES_NE_LIST(QP_DECLARE_LAUNCHERS, onepassc_u0)
+QP_ONEPASS_CLASSES_NE_LIST(QP_DECLARE_LAUNCHERS, onepassc_u1)
 
-static bool onepass_enabled() {      // QPSIM_COLL_ONEPASS=0: the three-launch split kernels (A/B timing, tests)
-  const char* e = getenv("QPSIM_COLL_ONEPASS");
-  return !e || atoi(e) != 0;
-}
+QP_DEFINE_LOOKUP(onepass, QP_ONEPASS_NE_LIST(QP_LOOKUP_CASE, onepass))
+QP_DEFINE_LOOKUP(onepassc_u0, QP_ONEPASS_CLASSES_NE_LIST(QP_LOOKUP_CASE, onepassc_u0))
+QP_DEFINE_LOOKUP(onepassc_u1, QP_ONEPASS_CLASSES_NE_LIST(QP_LOOKUP_CASE, onepassc_u1))
 
-// One gap class.  False when this (NE, processes) has no one-pass instantiation, a needed table is missing, or the kernel
-// family is switched off: the caller then takes the split kernels.
-bool collision_onepass_dispatch(const qp_collision_tables& tb, double* stash, const uint8_t* flags, long ncell,
-                                const double* sin_, double* sout, double* ph, double dE, double dt, bool s, bool r, bool u,
-                                hipStream_t stream) {
-  if (!onepass_enabled() || tb.nclass != 1 || !(s || r)) return false;
-  if ((s && !tb.ks0_diag) || (r && !tb.kr0_anti2)) return false;
+// The two one-pass routes of collision_route.  Gap classes: the separable kernel tables (gap_sq, kr_amp, ks_amp, pair_inv)
+// instead of kr0 / ks0 and their diagonal-major copies - the same kernel with K formed per lane.
+void collision_onepass_dispatch(Route route, const qp_collision_tables& t, const CollCall& c) {
   OnePassView v{};
-  v.base = CollFastView{tb.kr0, tb.ks0, tb.rho, tb.diag_bin, tb.anti_bin, stash, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        nullptr, 0.0};
-  v.ksd = tb.ks0_diag;
-  v.kra2 = tb.kr0_anti2;
   onepass_launcher_t fn = nullptr;
-  switch (tb.ne) {
-    case 50: fn = (s && r) ? onepass_50_11 : r ? onepass_50_01 : onepass_50_10; break;
-    case 40: fn = (s && r) ? onepass_40_11 : r ? onepass_40_01 : onepass_40_10; break;
-    case 32: fn = (s && r) ? onepass_32_11 : r ? onepass_32_01 : onepass_32_10; break;
-    case 30: fn = (s && r) ? onepass_30_11 : r ? onepass_30_01 : onepass_30_10; break;
-    default: return false;
+  if (route == QP_ROUTE_ONEPASS) {
+    v.base = CollFastView{t.kr0, t.ks0, t.rho, t.diag_bin, t.anti_bin, c.stash, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, 0.0};
+    v.ksd = t.ks0_diag;
+    v.kra2 = t.kr0_anti2;
+    fn = find_onepass(t.ne, c.s, c.r);
+  } else {
+    v.base = CollFastView{nullptr, nullptr, t.rho, t.diag_bin, t.anti_bin, c.stash, t.cls, t.gap_sq,
+                          c.r ? t.kr_amp : nullptr, c.s ? t.ks_amp : nullptr, t.pair_inv, nullptr, 0.0};
+    v.nclass = t.nclass;
+    fn = c.u ? find_onepassc_u1(t.ne, c.s, c.r) : find_onepassc_u0(t.ne, c.s, c.r);
   }
-  fn(v, flags, ncell, sin_, sout, ph, dE, dt, u, stream);
-  return true;
+  assert(fn && "collision_route chose a one-pass route for a size without a launcher");
+  fn(v, c);
 }
-
-// Gap classes (nclass > 1) with the separable kernel tables (gap_sq, kr_amp, ks_amp, pair_inv): the same kernel with K formed
-// per lane.  False when this (NE, processes) has no instantiation or a table is missing: the caller takes the split kernels.
-bool collision_onepass_dispatch_classes(const qp_collision_tables& tb, double* stash, const uint8_t* flags, long ncell,
-                                        const double* sin_, double* sout, double* ph, double dE, double dt, bool s, bool r,
-                                        bool u, hipStream_t stream) {
-  if (!onepass_enabled() || tb.nclass < 2 || tb.nclass > kOnePassMaxClasses || !(s || r)) return false;
-  if (!tb.cls || !tb.gap_sq || !tb.pair_inv || (s && !tb.ks_amp) || (r && !tb.kr_amp)) return false;
-  onepass_launcher_t fn = nullptr;
-  switch (tb.ne) {
-    case 50:
-      fn = (s && r) ? (u ? onepass_classes_50_11_u1 : onepass_classes_50_11_u0)
-           : r      ? (u ? onepass_classes_50_01_u1 : onepass_classes_50_01_u0)
-                    : (u ? onepass_classes_50_10_u1 : onepass_classes_50_10_u0);
-      break;
-    default: break;
-  }
-  if (!fn) return false;
-  OnePassView v{};
-  v.base = CollFastView{nullptr, nullptr, tb.rho, tb.diag_bin, tb.anti_bin, stash, tb.cls, tb.gap_sq, r ? tb.kr_amp : nullptr,
-                        s ? tb.ks_amp : nullptr, tb.pair_inv, nullptr, 0.0};
-  v.nclass = tb.nclass;
-  fn(v, flags, ncell, sin_, sout, ph, dE, dt, u, stream);
-  return true;
-}
-
-int collision_onepass_supported(int ne) { return (ne == 50 || ne == 40 || ne == 32 || ne == 30) ? 1 : 0; }
 
 }  // namespace qp

@@ -55,7 +55,6 @@ struct OnePassView {
 };
 
 constexpr int kOnePassThreads = 256;
-constexpr int kOnePassMaxClasses = 16;      // rows of the per-class rho table the LDS image of a PARAM kernel holds
 
 // compact (anti)diagonal-major order of the unordered pairs phase 2 visits: diagonal k >= 1 holds (i, i - k) for
 // i = k .. NE-1, anti-diagonal m holds (i, m - i) for i = ceil(m / 2) .. min(m, NE-1)
@@ -486,46 +485,28 @@ collision_onepass_kernel(OnePassView w, const uint8_t* __restrict__ flags, long 
 #undef QP_LDS_D
 }
 
-typedef void (*onepass_launcher_t)(const OnePassView&, const uint8_t*, long, const double*, double*, double*, double, double,
-                                   bool, hipStream_t);
-
-template <int NE, int TB, bool S, bool R, int PF, int WAVES, int G = 7, int G2 = 4, int PF2 = 12, bool PARAM = false>
-static void onepass_launch(const OnePassView& v, const uint8_t* flags, long ncell, const double* sin_, double* sout,
-                           double* ph, double dE, double dt, bool u, hipStream_t stream) {
-  const unsigned blocks = (unsigned)((ncell + kOnePassThreads - 1) / kOnePassThreads);
-  if (u)
-    hipLaunchKernelGGL((collision_onepass_kernel<NE, TB, S, R, true, PF, WAVES, G, G2, PF2, PARAM>), dim3(blocks), dim3(kOnePassThreads), 0, stream, v, flags,
-                       ncell, sin_, sout, ph, dE, dt);
+// the launcher families of the one-pass kernel (qp_collision_dispatch.h).  One gap class: both phonon modes in one unit.
+template <int NE, bool S, bool R, int TB, int PF, int WAVES>
+static void launch_onepass(const OnePassView& v, const CollCall& c) {
+  const unsigned blocks = (unsigned)((c.ncell + kOnePassThreads - 1) / kOnePassThreads);
+  if (c.u)
+    hipLaunchKernelGGL((collision_onepass_kernel<NE, TB, S, R, true, PF, WAVES>), dim3(blocks), dim3(kOnePassThreads), 0,
+                       c.stream, v, c.flags, c.ncell, c.sin, c.sout, c.ph, c.dE, c.dt);
   else
-    hipLaunchKernelGGL((collision_onepass_kernel<NE, TB, S, R, false, PF, WAVES, G, G2, PF2, PARAM>), dim3(blocks), dim3(kOnePassThreads), 0, stream, v,
-                       flags, ncell, sin_, sout, ph, dE, dt);
+    hipLaunchKernelGGL((collision_onepass_kernel<NE, TB, S, R, false, PF, WAVES>), dim3(blocks), dim3(kOnePassThreads), 0,
+                       c.stream, v, c.flags, c.ncell, c.sin, c.sout, c.ph, c.dE, c.dt);
 }
-
-// qp::onepass_<NE>_<S><R>: the entries qp_collision_onepass.hip looks up
-#define QP_DEFINE_ONEPASS(N, TB, S, R, PF, WAVES)                                                                            \
-  void onepass_##N##_##S##R(const OnePassView& v, const uint8_t* flags, long ncell, const double* sin_, double* sout,       \
-                            double* ph, double dE, double dt, bool u, hipStream_t stream) {                                 \
-    onepass_launch<N, TB, S != 0, R != 0, PF, WAVES>(v, flags, ncell, sin_, sout, ph, dE, dt, u, stream);                    \
-  }
-// gap-class form: qp::onepass_classes_<NE>_<S><R>_u<UPD>, one kernel per unit (each takes ~4 minutes to compile)
-#define QP_DEFINE_ONEPASS_CLASSES(N, TB, S, R, U, PF, WAVES, G, G2, PF2)                                                    \
-  void onepass_classes_##N##_##S##R##_u##U(const OnePassView& v, const uint8_t* flags, long ncell, const double* sin_,     \
-                                           double* sout, double* ph, double dE, double dt, bool, hipStream_t stream) {     \
-    const unsigned blocks = (unsigned)((ncell + kOnePassThreads - 1) / kOnePassThreads);                                   \
-    hipLaunchKernelGGL((collision_onepass_kernel<N, TB, S != 0, R != 0, U != 0, PF, WAVES, G, G2, PF2, true>), dim3(blocks), \
-                       dim3(kOnePassThreads), 0, stream, v, flags, ncell, sin_, sout, ph, dE, dt);                          \
-  }
-#define QP_DECLARE_ONEPASS_CLASSES(N, S, R)                                                                                 \
-  void onepass_classes_##N##_##S##R##_u0(const OnePassView&, const uint8_t*, long, const double*, double*, double*, double, \
-                                         double, bool, hipStream_t);                                                       \
-  void onepass_classes_##N##_##S##R##_u1(const OnePassView&, const uint8_t*, long, const double*, double*, double*, double, \
-                                         double, bool, hipStream_t);
-#define QP_DECLARE_ONEPASS(N)                                                                                              \
-  void onepass_##N##_11(const OnePassView&, const uint8_t*, long, const double*, double*, double*, double, double, bool,    \
-                        hipStream_t);                                                                                       \
-  void onepass_##N##_01(const OnePassView&, const uint8_t*, long, const double*, double*, double*, double, double, bool,    \
-                        hipStream_t);                                                                                       \
-  void onepass_##N##_10(const OnePassView&, const uint8_t*, long, const double*, double*, double*, double, double, bool,    \
-                        hipStream_t);
+// Gap-class form: one kernel per unit (each takes ~4 minutes to compile), so frozen (u0) and dynamic (u1) phonons are
+// families of their own and the dispatcher chooses between them.
+template <int NE, bool S, bool R, bool U, int TB, int PF, int WAVES, int G, int G2, int PF2>
+static void launch_onepassc(const OnePassView& v, const CollCall& c) {
+  const unsigned blocks = (unsigned)((c.ncell + kOnePassThreads - 1) / kOnePassThreads);
+  hipLaunchKernelGGL((collision_onepass_kernel<NE, TB, S, R, U, PF, WAVES, G, G2, PF2, true>), dim3(blocks),
+                     dim3(kOnePassThreads), 0, c.stream, v, c.flags, c.ncell, c.sin, c.sout, c.ph, c.dE, c.dt);
+}
+template <int NE, bool S, bool R, int... TILING>
+static void launch_onepassc_u0(const OnePassView& v, const CollCall& c) { launch_onepassc<NE, S, R, false, TILING...>(v, c); }
+template <int NE, bool S, bool R, int... TILING>
+static void launch_onepassc_u1(const OnePassView& v, const CollCall& c) { launch_onepassc<NE, S, R, true, TILING...>(v, c); }
 
 }  // namespace qp

@@ -2,5 +2,5 @@
 #include "qp_collision_onepass.inc"
 
 namespace qp {
-QP_DEFINE_ONEPASS(50, 14, 1, 1, 8, 2)
+QP_DEFINE_LAUNCHER(50, onepass, 1, 1, 14, 8, 2)
 }  // namespace qp

@@ -3,5 +3,5 @@
 #include "qp_collision_onepass.inc"
 
 namespace qp {
-QP_DEFINE_ONEPASS_CLASSES(50, 13, 1, 0, 1, 6, 2, 4, 3, 8)
+QP_DEFINE_LAUNCHER(50, onepassc_u1, 1, 0, 13, 6, 2, 4, 3, 8)
 }  // namespace qp

@@ -2,6 +2,6 @@
 #include "qp_collision_onepass.inc"
 
 namespace qp {
-QP_DEFINE_ONEPASS(50, 14, 0, 1, 8, 2)
-QP_DEFINE_ONEPASS(50, 14, 1, 0, 8, 2)
+QP_DEFINE_LAUNCHER(50, onepass, 0, 1, 14, 8, 2)
+QP_DEFINE_LAUNCHER(50, onepass, 1, 0, 14, 8, 2)
 }  // namespace qp

@@ -2,7 +2,7 @@
 #include "qp_collision_onepass.inc"
 
 namespace qp {
-QP_DEFINE_ONEPASS(40, 14, 1, 1, 8, 2)
-QP_DEFINE_ONEPASS(40, 14, 0, 1, 8, 2)
-QP_DEFINE_ONEPASS(40, 14, 1, 0, 8, 2)
+QP_DEFINE_LAUNCHER(40, onepass, 1, 1, 14, 8, 2)
+QP_DEFINE_LAUNCHER(40, onepass, 0, 1, 14, 8, 2)
+QP_DEFINE_LAUNCHER(40, onepass, 1, 0, 14, 8, 2)
 }  // namespace qp

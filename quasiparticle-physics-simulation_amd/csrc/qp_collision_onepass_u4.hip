@@ -2,7 +2,7 @@
 #include "qp_collision_onepass.inc"
 
 namespace qp {
-QP_DEFINE_ONEPASS(32, 16, 1, 1, 8, 2)
-QP_DEFINE_ONEPASS(32, 16, 0, 1, 8, 2)
-QP_DEFINE_ONEPASS(32, 16, 1, 0, 8, 2)
+QP_DEFINE_LAUNCHER(32, onepass, 1, 1, 16, 8, 2)
+QP_DEFINE_LAUNCHER(32, onepass, 0, 1, 16, 8, 2)
+QP_DEFINE_LAUNCHER(32, onepass, 1, 0, 16, 8, 2)
 }  // namespace qp

@@ -194,58 +194,19 @@ collision_pair_kernel(typename coll_view<MEMB>::type t, const uint8_t* __restric
   }
 }
 
-typedef void (*pair_launcherm_t)(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,
-                                 double, double, bool, hipStream_t);
-typedef void (*pair_launcher_t)(const CollFastView&, const uint8_t*, long, const double*, double*, double*, double, double,
-                                double, double, bool, hipStream_t);
-
+// the launcher families of the double half-step kernel (qp_collision_dispatch.h): shared tables, member tables
 template <int NE, bool S, bool R, bool MEMB = false>
-static void pair_launch(const typename coll_view<MEMB>::type& v, const uint8_t* flags, long ncell, const double* sin_,
-                        double* sout, double* ph, double dE, double dt_a, double dt_b, double gen, bool u,
-                        hipStream_t stream) {
-  const unsigned blocks = (unsigned)((ncell + 127) / 128);
-  if (u)
-    hipLaunchKernelGGL((collision_pair_kernel<NE, S, R, true, MEMB>), dim3(blocks), dim3(128), 0, stream, v, flags, ncell,
-                       sin_, sout, ph, dE, dt_a, dt_b, gen);
+static void launch_pair(const CollFastViewM& vm, const CollCall& c) {
+  const typename coll_view<MEMB>::type& v = vm;      // without MEMB: the CollFastView part, the kernel's whole argument
+  const unsigned blocks = (unsigned)((c.ncell + 127) / 128);
+  if (c.u)
+    hipLaunchKernelGGL((collision_pair_kernel<NE, S, R, true, MEMB>), dim3(blocks), dim3(128), 0, c.stream, v, c.flags,
+                       c.ncell, c.sin, c.sout, c.ph, c.dE, c.dt, c.dt_b, c.gen);
   else
-    hipLaunchKernelGGL((collision_pair_kernel<NE, S, R, false, MEMB>), dim3(blocks), dim3(128), 0, stream, v, flags, ncell,
-                       sin_, sout, ph, dE, dt_a, dt_b, gen);
+    hipLaunchKernelGGL((collision_pair_kernel<NE, S, R, false, MEMB>), dim3(blocks), dim3(128), 0, c.stream, v, c.flags,
+                       c.ncell, c.sin, c.sout, c.ph, c.dE, c.dt, c.dt_b, c.gen);
 }
-
-#define QP_DEFINE_PAIR(N)                                                                                                  \
-  void pair_launcher_##N##_11(const CollFastView& v, const uint8_t* f, long nc, const double* si, double* so, double* ph,  \
-                              double dE, double da, double db, double g, bool u, hipStream_t s) {                          \
-    pair_launch<N, true, true>(v, f, nc, si, so, ph, dE, da, db, g, u, s);                                                 \
-  }                                                                                                                        \
-  void pair_launcher_##N##_01(const CollFastView& v, const uint8_t* f, long nc, const double* si, double* so, double* ph,  \
-                              double dE, double da, double db, double g, bool u, hipStream_t s) {                          \
-    pair_launch<N, false, true>(v, f, nc, si, so, ph, dE, da, db, g, u, s);                                                \
-  }                                                                                                                        \
-  void pair_launcher_##N##_10(const CollFastView& v, const uint8_t* f, long nc, const double* si, double* so, double* ph,  \
-                              double dE, double da, double db, double g, bool u, hipStream_t s) {                          \
-    pair_launch<N, true, false>(v, f, nc, si, so, ph, dE, da, db, g, u, s);                                                \
-  }
-
-// member-class variant: qp::pair_launcherm_<N>_<S><R>
-#define QP_DEFINE_PAIRM(N)                                                                                                 \
-  void pair_launcherm_##N##_11(const CollFastViewM& v, const uint8_t* f, long nc, const double* si, double* so, double* ph, \
-                               double dE, double da, double db, double g, bool u, hipStream_t s) {                         \
-    pair_launch<N, true, true, true>(v, f, nc, si, so, ph, dE, da, db, g, u, s);                                           \
-  }                                                                                                                        \
-  void pair_launcherm_##N##_01(const CollFastViewM& v, const uint8_t* f, long nc, const double* si, double* so, double* ph, \
-                               double dE, double da, double db, double g, bool u, hipStream_t s) {                         \
-    pair_launch<N, false, true, true>(v, f, nc, si, so, ph, dE, da, db, g, u, s);                                          \
-  }                                                                                                                        \
-  void pair_launcherm_##N##_10(const CollFastViewM& v, const uint8_t* f, long nc, const double* si, double* so, double* ph, \
-                               double dE, double da, double db, double g, bool u, hipStream_t s) {                         \
-    pair_launch<N, true, false, true>(v, f, nc, si, so, ph, dE, da, db, g, u, s);                                          \
-  }
-#define QP_DECLARE_PAIRM(N)                                                                                                \
-  void pair_launcherm_##N##_11(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,\
-                               double, double, bool, hipStream_t);                                                         \
-  void pair_launcherm_##N##_01(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,\
-                               double, double, bool, hipStream_t);                                                         \
-  void pair_launcherm_##N##_10(const CollFastViewM&, const uint8_t*, long, const double*, double*, double*, double, double,\
-                               double, double, bool, hipStream_t);
+template <int NE, bool S, bool R>
+static void launch_pairm(const CollFastViewM& v, const CollCall& c) { launch_pair<NE, S, R, true>(v, c); }
 
 }  // namespace qp

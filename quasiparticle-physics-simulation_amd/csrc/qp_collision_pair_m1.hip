@@ -3,12 +3,12 @@
 #include "qp_collision_pair.inc"
 
 namespace qp {
-QP_DEFINE_PAIRM(4)
-QP_DEFINE_PAIRM(5)
-QP_DEFINE_PAIRM(6)
-QP_DEFINE_PAIRM(7)
-QP_DEFINE_PAIRM(8)
-QP_DEFINE_PAIRM(9)
-QP_DEFINE_PAIRM(10)
-QP_DEFINE_PAIRM(11)
+QP_DEFINE_LAUNCHERS(4, pairm)
+QP_DEFINE_LAUNCHERS(5, pairm)
+QP_DEFINE_LAUNCHERS(6, pairm)
+QP_DEFINE_LAUNCHERS(7, pairm)
+QP_DEFINE_LAUNCHERS(8, pairm)
+QP_DEFINE_LAUNCHERS(9, pairm)
+QP_DEFINE_LAUNCHERS(10, pairm)
+QP_DEFINE_LAUNCHERS(11, pairm)
 }  // namespace qp

@@ -3,7 +3,7 @@
 #include "qp_collision_pair.inc"
 
 namespace qp {
-QP_DEFINE_PAIRM(12)
-QP_DEFINE_PAIRM(13)
-QP_DEFINE_PAIRM(14)
+QP_DEFINE_LAUNCHERS(12, pairm)
+QP_DEFINE_LAUNCHERS(13, pairm)
+QP_DEFINE_LAUNCHERS(14, pairm)
 }  // namespace qp

@@ -3,6 +3,6 @@
 #include "qp_collision_pair.inc"
 
 namespace qp {
-QP_DEFINE_PAIRM(15)
-QP_DEFINE_PAIRM(16)
+QP_DEFINE_LAUNCHERS(15, pairm)
+QP_DEFINE_LAUNCHERS(16, pairm)
 }  // namespace qp

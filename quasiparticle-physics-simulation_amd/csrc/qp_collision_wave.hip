@@ -17,37 +17,9 @@
 // deterministic; otherwise (unstructured maps) LDS atomics (ds_add_f64) are used.
 // Every shared access is written as lds[integer index]: pointer selects or integer round-trips of the base make the
 // compiler fall back to flat (generic address space) accesses.
-#include "qp_common.h"
+#include "qp_collision_dispatch.h"
 
 namespace qp {
-
-struct WaveCollView {
-  int ne, nw, nclass;
-  const double* kr0;
-  const double* ks0;
-  const double* rho;
-  const int32_t* idx_diff;
-  const int32_t* idx_sum;
-  const int8_t* sign;
-  const int32_t* cls;
-  const int32_t* diag_bin;   // non-NULL: the host vouches for the |i-j| / i+j structure of the maps
-  const int32_t* anti_bin;
-};
-
-__device__ __forceinline__ double relax_update_w(double n, double gain, double loss, double dt) {
-  const double mu = fmax(loss, 0.0);
-  const double P = fmax(gain + (mu - loss) * n, 0.0);
-  const double decay = exp(-mu * dt);
-  const double coeff = (mu < 1e-14) ? dt : (1.0 - decay) / mu;
-  return fmax(decay * n + coeff * P, 0.0);
-}
-
-__device__ __forceinline__ double affine_update_w(double y, double a, double b, double dt) {
-  const double xx = fmin(fmax(b * dt, -80.0), 80.0);
-  const double ex = exp(xx);
-  const double coeff = (fabs(b) < 1e-14) ? dt : (ex - 1.0) / b;
-  return fmax(ex * y + coeff * a, 0.0);
-}
 
 __device__ __forceinline__ double bcast(double x, int srclane) {
   const unsigned long long u = __double_as_longlong(x);
@@ -134,13 +106,13 @@ __global__ void __launch_bounds__(64 * WAVES) collision_wave_kernel(WaveCollView
         }
       }
     }
-    n[k] = relax_update_w(ni, dE * qi * g_s + 2.0 * dE * qi * g_r, dE * l_s + 2.0 * dE * l_r, dt);
+    n[k] = relax_update(ni, dE * qi * g_s + 2.0 * dE * qi * g_r, dE * l_s + 2.0 * dE * l_r, dt);
     __builtin_amdgcn_wave_barrier();
     if (do_ph) {
 #pragma unroll
       for (int s = 0; s < MAXBINS; ++s) {
         const int w = lane + 64 * s;
-        if (w < NW) pb[s][k] = affine_update_w(pb[s][k], lds[o_A + w], lds[o_A + w] - lds[o_B + w], dt);
+        if (w < NW) pb[s][k] = affine_update(pb[s][k], lds[o_A + w], lds[o_A + w] - lds[o_B + w], dt);
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -164,20 +136,16 @@ __global__ void __launch_bounds__(64 * WAVES) collision_wave_kernel(WaveCollView
   }
 }
 
-// returns false when the shape is outside this kernel's range
-bool collision_wave_dispatch(const WaveCollView& v, bool structured, const uint8_t* flags, long ncell, const double* sin_,
-                             double* sout, double* ph, double dE, double dt, int en_r, int en_s, int upd,
-                             hipStream_t stream) {
-  if (v.ne > 64 || v.nw > 64 * MAXBINS) return false;
-  const unsigned blocks = (unsigned)((ncell + (long)PB * WAVES - 1) / ((long)PB * WAVES));
+// the caller (collision_route) has checked the kernel's range: ne <= 64, nw <= 64 MAXBINS
+void collision_wave_dispatch(const WaveCollView& v, bool structured, const CollCall& c) {
+  const unsigned blocks = (unsigned)((c.ncell + (long)PB * WAVES - 1) / ((long)PB * WAVES));
   const size_t shmem = (size_t)WAVES * 3 * v.nw * sizeof(double);
   if (structured)
-    hipLaunchKernelGGL(collision_wave_kernel<false>, dim3(blocks), dim3(64 * WAVES), shmem, stream, v, flags, ncell, sin_,
-                       sout, ph, dE, dt, en_r, en_s, upd);
+    hipLaunchKernelGGL(collision_wave_kernel<false>, dim3(blocks), dim3(64 * WAVES), shmem, c.stream, v, c.flags, c.ncell,
+                       c.sin, c.sout, c.ph, c.dE, c.dt, (int)c.r, (int)c.s, (int)c.u);
   else
-    hipLaunchKernelGGL(collision_wave_kernel<true>, dim3(blocks), dim3(64 * WAVES), shmem, stream, v, flags, ncell, sin_,
-                       sout, ph, dE, dt, en_r, en_s, upd);
-  return true;
+    hipLaunchKernelGGL(collision_wave_kernel<true>, dim3(blocks), dim3(64 * WAVES), shmem, c.stream, v, c.flags, c.ncell,
+                       c.sin, c.sout, c.ph, c.dE, c.dt, (int)c.r, (int)c.s, (int)c.u);
 }
 
 }  // namespace qp

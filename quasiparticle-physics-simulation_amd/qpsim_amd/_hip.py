@@ -42,6 +42,11 @@ class CollisionTables(_SizedStructure):
                 ("ks0_diag", c_dp), ("kr0_anti2", c_dp)]
 
 
+# qp_collision_route_kind: what qp_collision_route returns for tables it accepts
+(ROUTE_ONEPASS, ROUTE_REGISTER, ROUTE_REGISTER_MEMBERS, ROUTE_ONEPASS_CLASSES, ROUTE_REGISTER_CLASSES, ROUTE_WAVE,
+ ROUTE_GENERIC, ROUTE_COPY) = range(8)
+
+
 class RectPlan(C.Structure):
     """Opaque ``qp_adi_rect_plan``; only ever handled by pointer."""
 
@@ -118,6 +123,7 @@ SIGNATURES = {
     "qp_collision_onepass_available": (C.c_int, [C.c_int32]),
     "qp_collision_member_tables_available": (C.c_int, [C.c_int32]),
     "qp_collision_pair_available": (C.c_int, [C.c_int32]),
+    "qp_collision_route": (C.c_int, [C.POINTER(CollisionTables), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "qp_collision_double_step_guarded": (C.c_int, [C.POINTER(CollisionTables), c_dp, C.c_int64, c_dp, c_dp, c_dp, C.c_double,
                                                    C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double,
                                                    c_dp, c_dp, c_dp, c_dp]),

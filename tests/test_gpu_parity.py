@@ -690,18 +690,27 @@ def test_wave_collision_kernel_matches_generic_and_oracle(O, ne, fmax, nclass, e
 
 
 def test_collision_kernel_selection():
+    import ctypes as C
+    from qpsim_amd import _hip
     from qpsim_amd import tables as T
     from qpsim_amd.engine import CompiledGeometry, Engine, link_flags
     mask = np.ones((1, 8), dtype=bool)
     z = np.zeros(mask.shape)
     eng = Engine(CompiledGeometry(mask, 1.0, link_flags(mask), z, z, z, z))
+    family = {_hip.ROUTE_WAVE: "wave", _hip.ROUTE_GENERIC: "generic"}
+    family.update({r: "register" for r in (_hip.ROUTE_ONEPASS, _hip.ROUTE_REGISTER, _hip.ROUTE_REGISTER_MEMBERS,
+                                           _hip.ROUTE_ONEPASS_CLASSES, _hip.ROUTE_REGISTER_CLASSES)})
 
     def pick(ne, fmax, nclass=1):
         E, _ = T.build_energy_grid(180.0, 1.0, fmax, ne)
         om, idd, ids, sg = T.build_phonon_frequency_map(E)
         rho = np.ones((nclass, ne))
         k = np.zeros((nclass, ne, ne))
-        return eng.make_collision_tables(k, k, rho, idd, ids, sg, np.zeros(8, dtype=int) if nclass > 1 else None)["kernel"]
+        h = eng.make_collision_tables(k, k, rho, idd, ids, sg, np.zeros(8, dtype=int) if nclass > 1 else None)
+        # the engine's own rule agrees with the library's: all processes on, scratch present
+        route = _hip.load().qp_collision_route(C.byref(h["struct"]), 8, 1, 1, 1, 1)
+        assert family[route] == h["kernel"], (ne, fmax, nclass, route)
+        return h["kernel"]
 
     assert pick(12, 3.0) == "register" and pick(16, 10.0) == "register"
     assert pick(24, 3.0) == "register" and pick(50, 10.0) == "register"      # instantiated sizes incl. the reference default
