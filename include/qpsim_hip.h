@@ -222,7 +222,8 @@ int qp_collision_register_kernel_available(int32_t ne);
 /* 1 when the one-pass kernel (ks0_diag / kr0_anti2 above) is instantiated for `ne` energy bins: ne = 30, 32, 40 and 50 (the
  * reference's default num_energy_bins, solver.py:1012). */
 int qp_collision_onepass_available(int32_t ne);
-/* 1 when the register-resident kernel also has its gap-class variant for `ne` (single-pass sizes: ne <= 16, 18, 20, 24, 30). */
+/* 1 when the register-resident kernel also has its gap-class variant for `ne`: the sizes of
+ * qp_collision_register_kernel_available (single pass for ne = 2 ... 16, 18, 20, 24, 30; three launches for 32, 40, 50). */
 int qp_collision_register_kernel_classes(int32_t ne);
 /* 1 when the single-pass and the double half-step register kernels are instantiated in their member-table form
  * (QP_COLL_MEMBER_CLASSES) for `ne`: ne = 4 ... 16. */

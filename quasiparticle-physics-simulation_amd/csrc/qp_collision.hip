@@ -145,7 +145,8 @@ Route collision_route(const qp_collision_tables& t, long ncell, bool en_r, bool 
   const bool reg = t.diag_bin && !(t.flags & (QP_COLL_FORCE_GENERIC | QP_COLL_FORCE_WAVE)) && shared_ok && ncell < (1L << 28);
 
   if (reg && t.nclass == 1) {
-    // 32 <= ne <= 64 with the diagonal-major tables of the enabled processes: one launch instead of the three of the split
+    // ne = 30, 32, 40, 50 with the diagonal-major tables of the enabled processes: one launch (instead of the three of the
+    // split for ne >= 32)
     if (collision_onepass_supported(t.ne) && (s || r) && (!s || t.ks0_diag) && (!r || t.kr0_anti2) && onepass_enabled())
       return QP_ROUTE_ONEPASS;
     // no process enabled: relaxation with zero gain and loss, which the copy kernel does for any tables

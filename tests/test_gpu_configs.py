@@ -3,10 +3,15 @@ whole problem: sampled-pixel oracle checks (the collision update is pixel-local)
 ensembles, and an extended-precision restatement that prices the tolerances of the phonon update."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import pytest
 
+from collision_grids import unmerged_fmax
 from golden_utils import rel_err
+from test_collision_route_host import AVAILABLE
+from test_gpu_parity import PROCESS_COMBOS
 
 pytestmark = pytest.mark.gpu
 
@@ -523,12 +528,32 @@ def test_one_pass_ne50_gap_class_kernel_equals_the_split_kernels(monkeypatch, co
         assert np.array_equal(outs["1"][1], ph)
 
 
-@pytest.mark.parametrize("ne,combo", [(12, (True, True, True)), (12, (True, False, False)), (12, (False, True, True)),
-                                      (8, (True, True, True)), (8, (True, True, False)), (16, (True, True, True)), (5, (False, True, True))])
+# the seven cases this test began with keep their place (and ids); then every other size x process combination of
+# QP_PAIR_NE_LIST.  The single-call kernels of every size are oracle-checked in test_gpu_collision_instantiations.py, so
+# bit-equality with the two-call sequence carries that check over.
+_PAIR_FIRST = [(12, (True, True, True)), (12, (True, False, False)), (12, (False, True, True)), (8, (True, True, True)),
+               (8, (True, True, False)), (16, (True, True, True)), (5, (False, True, True))]
+PAIR_CASES = _PAIR_FIRST + [(ne, c) for ne in AVAILABLE["qp_collision_pair_available"] for c in PROCESS_COMBOS
+                            if (ne, c) not in _PAIR_FIRST]
+assert len(PAIR_CASES) == 6 * len(AVAILABLE["qp_collision_pair_available"]) and 12 in AVAILABLE["qp_collision_pair_available"]
+
+
+@pytest.mark.parametrize("ne,combo", PAIR_CASES)
 def test_double_half_step_kernel_equals_two_calls_bit_for_bit(ne, combo):
     """qp_collision_double_step_guarded = guarded half-step + generation term + half-step with the intermediate state kept
     in registers: quasiparticle planes, phonon planes and the guard statistics of the INTERMEDIATE state must equal the
     two-call sequence exactly (same arithmetic, operation for operation), on a masked grid with a ragged last block."""
+    _double_half_step_case(ne, combo, 0.05, 0.03, 2.5e-7)
+
+
+@pytest.mark.parametrize("dt_a,dt_b,gen", [(0.0, 0.05, 2.5e-7), (25.0, 1e-7, 2.5e-7), (0.05, 0.03, 0.0)])
+def test_double_half_step_kernel_at_the_ends_of_the_step_range(dt_a, dt_b, gen):
+    """A first half-step that changes nothing, a clipped exponent followed by a rounding-dominated one, no generation."""
+    _double_half_step_case(12, (True, True, True), dt_a, dt_b, gen)
+
+
+def _double_half_step_case(ne, combo, dt_a, dt_b, gen):
+    from qpsim_amd import _hip
     from qpsim_amd import tables as T
     from qpsim_amd.engine import CompiledGeometry, Engine, link_flags
     en_r, en_s, upd = combo
@@ -537,7 +562,7 @@ def test_double_half_step_kernel_equals_two_calls_bit_for_bit(ne, combo):
     z = np.zeros(mask.shape)
     eng = Engine(CompiledGeometry(mask, 1.0, link_flags(mask), z, z, z, z))
     n = int(mask.sum())
-    E, dE = T.build_energy_grid(180.0, 1.0, 3.0, ne)
+    E, dE = T.build_energy_grid(180.0, 1.0, unmerged_fmax(ne), ne)      # 3.0 but for NE = 7, 13, 14 (tests/collision_grids.py)
     om, idx_d, idx_s, sg = T.build_phonon_frequency_map(E)
     rho = T.dynes_density_of_states(E, 180.0, 0.1)
     kr, ks = T.recombination_kernel_base(E, 180.0, 500.0, 1.2), T.scattering_kernel_base(E, 180.0, 400.0, 1.2)
@@ -545,7 +570,8 @@ def test_double_half_step_kernel_equals_two_calls_bit_for_bit(ne, combo):
     ph = T.thermal_phonon_occupation(om, 0.3)[:, None] * (0.5 + rng.random((om.size, n)))
     tab = eng.make_collision_tables(kr[None], ks[None], rho[None], idx_d, idx_s, sg)
     assert tab["kernel"] == "register" and tab["pair"]
-    dt_a, dt_b, gen = 0.05, 0.03, 2.5e-7
+    # the two-call sequence runs the single-step register kernel of this size
+    assert eng.lib.qp_collision_route(C.byref(tab["struct"]), eng.ncell, int(en_r), int(en_s), int(upd), 0) == _hip.ROUTE_REGISTER
     # two calls
     s0, p_two = eng.upload_packed(state), eng.upload_packed(ph)
     s1, s2 = eng.empty(ne, eng.ncell), eng.empty(ne, eng.ncell)

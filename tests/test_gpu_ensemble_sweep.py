@@ -9,6 +9,9 @@ import warnings
 import numpy as np
 import pytest
 
+from collision_grids import unmerged_fmax
+from test_collision_route_host import AVAILABLE
+
 pytestmark = pytest.mark.gpu
 
 ADI_TOL, CN_TOL = 2e-13, 1e-12          # the ensemble contract (tests/test_gpu_ensemble.py)
@@ -17,6 +20,11 @@ FLOOR = 1e-18
 MEMBER_PHYSICS = [(0.0, 440.0, 440.0, 1.2), (0.1, 300.0, 520.0, 1.0), (0.4, 650.0, 250.0, 1.5)]
 PROCESSES = [(True, True), (True, False), (False, True)]       # (recombination, scattering)
 SHAPES = {40: (4, 10), 64: (4, 16), 100: (4, 25), 128: (8, 16), 192: (12, 16)}
+# (ne, cells per member) of the kernel tests: every size of QP_MEMBER_NE_LIST at 192 cells (three waves per member, so the
+# 128-thread blocks straddle members), three of them also at one and two waves per member
+MEMBER_NE = AVAILABLE["qp_collision_member_tables_available"]
+MEMBER_SHAPES = [(ne, ncm) for ne in MEMBER_NE for ncm in ((64, 128, 192) if ne in (4, 12, 16) else (192,))]
+assert {4, 7, 9, 12, 13, 16} <= set(MEMBER_NE)
 
 
 @pytest.fixture(scope="module")
@@ -48,9 +56,10 @@ def rel_err(a, b):
 _SETUPS: dict = {}
 
 
-def _setup(ne, ncm, fmax=3.0):
+def _setup(ne, ncm, fmax=None):
     """Engine of one member's grid, the member-class tables of three members, each member's lone table, and inputs laid out
-    [bin][member][cell] (built once per shape)."""
+    [bin][member][cell] (built once per shape).  Default grid: the unmerged one of tests/collision_grids.py."""
+    fmax = unmerged_fmax(ne) if fmax is None else fmax
     key = (ne, ncm, fmax)
     if key in _SETUPS:
         return _SETUPS[key]
@@ -113,15 +122,18 @@ def _lone_step(s, dt, en_r, en_s, upd, guarded=False):
 
 @pytest.mark.parametrize("upd", [True, False])
 @pytest.mark.parametrize("en_r,en_s", PROCESSES)
-@pytest.mark.parametrize("ncm", [64, 128, 192])
-@pytest.mark.parametrize("ne", [4, 12, 16])
+@pytest.mark.parametrize("ne,ncm", MEMBER_SHAPES)
 def test_member_table_step_is_bit_equal_to_lone_table_calls(torch, lib, ne, ncm, en_r, en_s, upd):
     """ncm = 64 / 192: 128-thread blocks hold waves of two members, and at 3 x 64 cells the last block's second wave lies
     beyond the grid."""
+    from qpsim_amd import _hip
     s = _setup(ne, ncm)
     assert lib.qp_collision_member_tables_available(ne) == 1 and s["tab"]["kernel"] == "register"
     assert s["tab"]["struct"].flags & 8 and s["tab"]["nclass"] == 3
     eng, n = s["eng"], s["M"] * ncm
+    assert lib.qp_collision_route(C.byref(s["tab"]["struct"]), n, int(en_r), int(en_s), int(upd), 0) == _hip.ROUTE_REGISTER_MEMBERS
+    for lone in s["lone"]:
+        assert lib.qp_collision_route(C.byref(lone["struct"]), ncm, int(en_r), int(en_s), int(upd), 0) == _hip.ROUTE_REGISTER
     want_s, want_p, _ = _lone_step(s, 0.37, en_r, en_s, upd)
     out, ph = torch.full_like(s["state"], -7.0), s["ph"].clone()
     eng.collide(s["tab"], s["state"], out, ph, s["dE"], 0.37, en_r, en_s, upd, ncell=n, flags=s["flags"])
@@ -136,8 +148,7 @@ def test_member_table_step_is_bit_equal_to_lone_table_calls(torch, lib, ne, ncm,
 
 @pytest.mark.parametrize("upd", [True, False])
 @pytest.mark.parametrize("en_r,en_s", PROCESSES)
-@pytest.mark.parametrize("ncm", [64, 128, 192])
-@pytest.mark.parametrize("ne", [4, 12, 16])
+@pytest.mark.parametrize("ne,ncm", MEMBER_SHAPES)
 def test_member_table_guarded_step_is_bit_equal_with_per_member_guards(torch, lib, ne, ncm, en_r, en_s, upd):
     s = _setup(ne, ncm)
     eng = s["eng"]
@@ -152,8 +163,7 @@ def test_member_table_guarded_step_is_bit_equal_with_per_member_guards(torch, li
 
 @pytest.mark.parametrize("upd", [True, False])
 @pytest.mark.parametrize("en_r,en_s", PROCESSES)
-@pytest.mark.parametrize("ncm", [64, 128, 192])
-@pytest.mark.parametrize("ne", [4, 12, 16])
+@pytest.mark.parametrize("ne,ncm", MEMBER_SHAPES)
 def test_member_table_double_step_is_bit_equal_to_the_two_call_sequence(torch, lib, ne, ncm, en_r, en_s, upd):
     """qp_collision_double_step_guarded_members with member tables against, per member and with its single table,
     qp_collision_step_guarded(dt_first); += gen_amount on interior cells; qp_collision_step(dt_second)."""
@@ -191,7 +201,7 @@ def test_member_table_step_with_merged_phonon_bins(torch, lib):
     assert np.array_equal(out.cpu().numpy(), want_s) and np.array_equal(ph.cpu().numpy(), want_p)
 
 
-@pytest.mark.parametrize("ne", [4, 16])
+@pytest.mark.parametrize("ne", [4, 7, 9, 13, 16])
 def test_member_table_step_matches_the_cpu_oracle(torch, ne):
     from oracle import qp_oracle as O
     s = _setup(ne, 128)
