@@ -505,6 +505,13 @@ class Engine:
         self._red_idx = self._red_buf[2:]
         self._scratch = {}
         self._pinned_stream = None
+        # made at their first use: download staging rings, guard workspace, pinned guard read-back slots (lone: a ring;
+        # ensembles: result buffer + ring per ensemble size), device vectors of per-member generation amounts
+        self._dl_slots = None
+        self._guard_ws = None
+        self._guard_slots = None
+        self._mguard: dict = {}
+        self._amount_vectors: dict = {}
 
     # -- plumbing -------------------------------------------------------------------------------------------
     @property
@@ -564,7 +571,7 @@ class Engine:
         n = planes.shape[0]
         shape = (n, self.ny, self.nx) if full_shape is None else (n,) + tuple(full_shape)
         numel = int(np.prod(shape))
-        if not hasattr(self, "_dl_slots"):
+        if self._dl_slots is None:
             self._dl_stream = torch.cuda.Stream(device=self.device)
             # Two rings: a store point of a full-physics run enqueues up to four downloads (integrated frame, state, phonon
             # planes, phonon sum) - two of one plane, two of NE / Nw planes.  Each ring holds two store points' worth of its
@@ -932,14 +939,30 @@ class Engine:
                                            _ptr(h["ks0_diag"]), _ptr(h["kr0_anti2"]))
         return h
 
+    def _collision_scratch(self, tables, nc: int, en_r, en_s, update_phonons):
+        """What a collision call over ``nc`` pixels needs beside its planes: the phonon accumulator planes of the kernels
+        that are not ``fast``, the merged-bin stash of the register kernels, or None."""
+        planes = 0
+        if update_phonons and (en_r or en_s) and not tables["fast"]:
+            planes = tables["nw"]
+        if tables["kernel"] == "register" and tables["merged_slots"] and update_phonons and en_r and en_s:
+            planes = tables["merged_slots"]
+        return self.scratch("coll_acc", 2 * planes * nc) if planes else None
+
+    def _guard_workspace(self, nc: int, min_bytes: int = 0):
+        """The workspace of a guarded collision call over ``nc`` pixels (at least ``min_bytes``), grown when too small.  One
+        buffer serves the lone ``*_guarded`` calls and, through ``_members_ws``, the ``*_members`` calls and the per-member
+        guard: it only ever grows, and every user runs on the engine's one stream, one call after the other."""
+        nbytes = max(int(self.lib.qp_collision_guard_workspace_bytes(nc)), int(min_bytes))
+        if self._guard_ws is None or self._guard_ws.numel() < nbytes:
+            self._guard_ws = self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.device)
+        return self._guard_ws
+
     def collide(self, tables, state, state_out, phonon, dE, dt, en_r, en_s, update_phonons, ncell: int | None = None,
                 flags=None):
         """One collision update; ``ncell`` / ``flags`` override the engine's grid (ensembles: members x cells)."""
         nc = self.ncell if ncell is None else int(ncell)
-        need_acc = update_phonons and (en_r or en_s) and not tables["fast"]
-        acc = self.scratch("coll_acc", 2 * tables["nw"] * nc) if need_acc else None
-        if tables["kernel"] == "register" and tables["merged_slots"] and update_phonons and en_r and en_s:
-            acc = self.scratch("coll_acc", 2 * tables["merged_slots"] * nc)      # merged-bin stash
+        acc = self._collision_scratch(tables, nc, en_r, en_s, update_phonons)
         _hip.check(self.lib.qp_collision_step(C.byref(tables["struct"]), _ptr(self.d_flags if flags is None else flags), nc, _ptr(state),
                                               _ptr(state_out), _ptr(phonon), _ptr(acc), float(dE), float(dt),
                                               int(bool(en_r)), int(bool(en_s)), int(bool(update_phonons)), self.stream),
@@ -951,23 +974,16 @@ class Engine:
         single-pass register kernels reduce the statistics of the new densities while they are still in registers.
         Returns a ticket for ``pauli_stats_result`` (asynchronous read-back, as ``pauli_stats_launch``)."""
         nc = self.ncell if ncell is None else int(ncell)
-        need_acc = update_phonons and (en_r or en_s) and not tables["fast"]
-        acc = self.scratch("coll_acc", 2 * tables["nw"] * nc) if need_acc else None
-        if tables["kernel"] == "register" and tables["merged_slots"] and update_phonons and en_r and en_s:
-            acc = self.scratch("coll_acc", 2 * tables["merged_slots"] * nc)
-        nbytes = int(self.lib.qp_collision_guard_workspace_bytes(nc))
-        ws = getattr(self, "_guard_ws", None)
-        if ws is None or ws.numel() < nbytes:
-            ws = self._guard_ws = self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.device)
+        acc = self._collision_scratch(tables, nc, en_r, en_s, update_phonons)
+        ws = self._guard_workspace(nc)
         hv, hi, ev = self._guard_slot()
-        self._guard_ne = tables["ne"]
         _hip.check(self.lib.qp_collision_step_guarded(
             C.byref(tables["struct"]), _ptr(self.d_flags if flags is None else flags), nc, _ptr(state), _ptr(state_out),
             _ptr(phonon), _ptr(acc), float(dE), float(dt), int(bool(en_r)), int(bool(en_s)), int(bool(update_phonons)),
             float(floor), _ptr(ws), _ptr(self._red_vals), _ptr(self._red_idx), self.stream), "qp_collision_step_guarded")
         self._guard_copy(hv)
         ev.record(self.torch.cuda.current_stream(self.device))
-        return hv, hi, ev, nc
+        return hv, hi, ev, nc, tables["ne"]
 
     def collide_pair_guarded(self, tables, state, state_out, phonon, dE, dt_first, dt_second, gen_amount, en_r, en_s,
                              update_phonons, floor: float, ncell: int | None = None, flags=None):
@@ -975,12 +991,8 @@ class Engine:
         next step and that step's opening half-step as ONE pass over the state (``qp_collision_double_step_guarded``; only
         call when ``tables["pair"]``).  Returns the guard ticket of the step that closes (as ``collide_guarded``)."""
         nc = self.ncell if ncell is None else int(ncell)
-        nbytes = int(self.lib.qp_collision_guard_workspace_bytes(nc))
-        ws = getattr(self, "_guard_ws", None)
-        if ws is None or ws.numel() < nbytes:
-            ws = self._guard_ws = self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.device)
+        ws = self._guard_workspace(nc)
         hv, hi, ev = self._guard_slot()
-        self._guard_ne = tables["ne"]
         _hip.check(self.lib.qp_collision_double_step_guarded(
             C.byref(tables["struct"]), _ptr(self.d_flags if flags is None else flags), nc, _ptr(state), _ptr(state_out),
             _ptr(phonon), float(dE), float(dt_first), float(dt_second), float(gen_amount), int(bool(en_r)), int(bool(en_s)),
@@ -988,7 +1000,7 @@ class Engine:
             "qp_collision_double_step_guarded")
         self._guard_copy(hv)
         ev.record(self.torch.cuda.current_stream(self.device))
-        return hv, hi, ev, nc
+        return hv, hi, ev, nc, tables["ne"]
 
     GUARD_LAG = 3       # guard tickets a time loop may keep outstanding (GUARD_LAG + 1 pinned read-back slots)
 
@@ -997,7 +1009,7 @@ class Engine:
         has been enqueued, so the device always has queued work while the host reads (measured: lags 1, 3 and 6 give the
         same 0.067 / 0.084 / 0.455 ms per coupled NE = 12 step at 64^2 / 256^2 / 1024^2 - the loop is not host-bound)."""
         torch = self.torch
-        if not hasattr(self, "_guard_slots"):
+        if self._guard_slots is None:
             self._guard_slots, self._guard_host = [], {}
             for _ in range(self.GUARD_LAG + 1):
                 buf = torch.empty(4, dtype=torch.int64).pin_memory()          # host image of _red_buf
@@ -1031,21 +1043,20 @@ class Engine:
         torch = self.torch
         hv, hi, ev = self._guard_slot()
         nc = self.ncell if ncell is None else int(ncell)
-        self._guard_ne = tables["ne"]
         _hip.check(self.lib.qp_pauli_stats(_ptr(state), _ptr(tables["rho"]), _ptr(tables["cls"]),
                                            _ptr(self.d_flags if flags is None else flags), tables["ne"], tables["nclass"],
                                            nc, float(floor), _ptr(self._ws), _ptr(self._red_vals), _ptr(self._red_idx),
                                            self.stream), "qp_pauli_stats")
         self._guard_copy(hv)
         ev.record(torch.cuda.current_stream(self.device))
-        return hv, hi, ev, nc
+        return hv, hi, ev, nc, tables["ne"]
 
     def pauli_stats_result(self, ticket):
-        hv, hi, ev, nc = ticket
+        hv, hi, ev, nc, ne = ticket
         ev.synchronize()
         mx = float(hv[0])
         i0, i1 = int(hi[0]), int(hi[1])
-        i0 = min(max(i0, 0), nc * int(self._guard_ne) - 1)
+        i0 = min(max(i0, 0), nc * int(ne) - 1)
         top = (i0 // nc, i0 % nc)
         forb = None if i1 < 0 else (i1 // nc, i1 % nc)
         return mx, top, forb
@@ -1055,7 +1066,7 @@ class Engine:
         """Device result buffer [vals | argmax, forbidden per member] (members x 24 bytes: one read-back copy per ticket) and
         its ring of GUARD_LAG + 1 pinned host images, per ensemble size."""
         torch = self.torch
-        cache = self.__dict__.setdefault("_mguard", {})
+        cache = self._mguard
         if members not in cache:
             dev = torch.zeros(3 * members, dtype=torch.int64, device=self.device)
             ring = [(torch.empty(3 * members, dtype=torch.int64).pin_memory(), torch.cuda.Event())
@@ -1064,12 +1075,8 @@ class Engine:
         return cache[members]
 
     def _members_ws(self, ncell_member: int, members: int):
-        nbytes = max(int(self.lib.qp_collision_guard_workspace_bytes(ncell_member * members)),
-                     int(self.lib.qp_pauli_members_workspace_bytes(ncell_member, members)))
-        ws = getattr(self, "_mguard_ws", None)
-        if ws is None or ws.numel() < nbytes:
-            ws = self._mguard_ws = self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.device)
-        return ws
+        return self._guard_workspace(ncell_member * members,
+                                     self.lib.qp_pauli_members_workspace_bytes(ncell_member, members))
 
     def _members_launch(self, tables, ncell_member: int, members: int, call):
         """Runs ``call(ws, out_vals, out_idx)`` and enqueues the asynchronous read-back of its per-member results."""
@@ -1109,10 +1116,7 @@ class Engine:
                                 ncell_member: int, members: int, flags):
         """``collide_guarded`` over an ensemble with the guard reduced per member (``qp_collision_step_guarded_members``)."""
         nc = int(ncell_member) * int(members)
-        need_acc = update_phonons and (en_r or en_s) and not tables["fast"]
-        acc = self.scratch("coll_acc", 2 * tables["nw"] * nc) if need_acc else None
-        if tables["kernel"] == "register" and tables["merged_slots"] and update_phonons and en_r and en_s:
-            acc = self.scratch("coll_acc", 2 * tables["merged_slots"] * nc)
+        acc = self._collision_scratch(tables, nc, en_r, en_s, update_phonons)
 
         def call(ws, vals, idx):
             _hip.check(self.lib.qp_collision_step_guarded_members(
@@ -1142,24 +1146,30 @@ class Engine:
     def add_constant_members(self, state, amounts: tuple, ncell_member: int, members: int, flags):
         """state[f][m * ncell_member + c] += amounts[m] on interior cells.  The device vectors are cached by value: constant
         and pulse generation take few distinct per-member patterns, so no step uploads synchronously."""
-        cache = self.__dict__.setdefault("_amount_vectors", {})
         key = tuple(float(a) for a in amounts)
-        vec = cache.get(key)
+        vec = self._amount_vectors.get(key)
         if vec is None:
-            vec = cache[key] = self.torch.as_tensor(np.asarray(key, dtype=np.float64), device=self.device)
+            vec = self._amount_vectors[key] = self.upload_vector(key)
         nfield = state.numel() // (int(ncell_member) * int(members))
         _hip.check(self.lib.qp_add_constant_members(_ptr(flags), int(ncell_member), int(members), int(nfield), _ptr(state),
                                                     _ptr(vec), self.stream), "qp_add_constant_members")
 
-    def energy_integral(self, state, dE: float):
-        out = self.empty(self.ncell)
-        _hip.check(self.lib.qp_energy_integrate(_ptr(state), state.shape[0], self.ncell, float(dE), _ptr(out),
-                                                self.stream), "qp_energy_integrate")
+    def energy_integral(self, state, dE: float, ncell: int | None = None):
+        """dE * sum over the bins of ``state`` [NE, ncell]; ``ncell`` overrides the engine's grid (members x cells)."""
+        nc = self.ncell if ncell is None else int(ncell)
+        out = self.empty(nc)
+        _hip.check(self.lib.qp_energy_integrate(_ptr(state), state.numel() // nc, nc, float(dE), _ptr(out), self.stream),
+                   "qp_energy_integrate")
         return out
 
-    def weighted_sum(self, planes, weights):
-        out = self.empty(self.ncell)
-        w = self.torch.as_tensor(np.asarray(weights, dtype=np.float64), device=self.device)
-        _hip.check(self.lib.qp_weighted_sum(_ptr(planes), _ptr(w), planes.shape[0], self.ncell, _ptr(out), self.stream),
+    def weighted_sum(self, planes, weights, ncell: int | None = None):
+        """sum_k weights[k] planes[k]; ``weights`` on the host or already on the device, ``ncell`` as ``energy_integral``."""
+        nc = self.ncell if ncell is None else int(ncell)
+        out = self.empty(nc)
+        w = weights if self.torch.is_tensor(weights) else self.upload_vector(weights)
+        _hip.check(self.lib.qp_weighted_sum(_ptr(planes), _ptr(w), planes.numel() // nc, nc, _ptr(out), self.stream),
                    "qp_weighted_sum")
         return out
+
+    def upload_vector(self, values):
+        return self.torch.as_tensor(np.asarray(values, dtype=np.float64), device=self.device)

@@ -25,11 +25,10 @@ import warnings
 
 import numpy as np
 
-from . import _hip
 from . import solver as S
-from . import tables as _tb
 from .distributed import shard_members
-from .engine import Engine, _ptr
+from .engine import Engine
+from .timeloop import EnergyRun, Outputs, Schedule, energy_loop
 
 __all__ = ["run_2d_crank_nicolson_ensemble", "PER_MEMBER_KEYS", "SWEEP_KEYS", "member_arguments", "plan_batches",
            "generation_amounts", "last_run_stats"]
@@ -218,81 +217,23 @@ def _prefixed(m: int, fn, *args):
 
 def _run_batch_on_device(kws, ids, errors, device):
     a = kws[0]
-    M = len(kws)
     checked = [_prefixed(ids[j], S._checked_run_arguments, k["mask"], k["initial_field"], k["diffusion_coefficient"],
                          k["dt"], k["total_time"], k["store_every"], k["enable_diffusion"], k["enable_recombination"],
                          k["enable_scattering"], k["tau_0"], k["tau_s"], k["tau_r"], k["external_generation"],
                          k["phonon_history_out"]) for j, k in enumerate(kws)]
-    mask, _, store_every, n, tau_s_eff, tau_r_eff = checked[0]
+    mask, _, store_every, n, _, _ = checked[0]
     inits = [c[1] for c in checked]
     geom = S._run_geometry(mask, a["edges"], a["edge_conditions"], a["dx"], a["enable_diffusion"])
-    full_steps, rem, total_steps = S._step_plan(a["total_time"], a["dt"])
+    sched = Schedule(a["total_time"], a["dt"], store_every)
     eng = Engine(geom, device=device)
     eng.pin_stream()
-    ncm = eng.ncell
-    flags = eng.d_flags.reshape(-1).repeat(M)            # [member][cell]
-    stored = lambda step: step % store_every == 0 or step == total_steps  # noqa: E731
+    flags = eng.d_flags.reshape(-1).repeat(len(kws))     # [member][cell]
+    out = Outputs(mask, a["dx"], [k["progress_callback"] for k in kws])
     if not a["energy_gap"] > 0.0:
-        return _run_scalar_batch(eng, kws, inits, mask, rem, full_steps, total_steps, stored)
-    return _run_energy_batch(eng, kws, ids, errors, inits, mask, n, flags, [(c[4], c[5]) for c in checked], rem, full_steps,
-                             total_steps, stored)
-
-
-def _frames_async(eng, planes, mask):
-    return S._device_frames_async(eng, planes, mask)
-
-
-def _run_scalar_batch(eng, kws, inits, mask, rem, full_steps, total_steps, stored):
-    """Scalar mode (energy_gap == 0) for M members: one [M, ncell] field set (solver._run_scalar per member)."""
-    a, M = kws[0], len(kws)
-    dx = a["dx"]
-    u_host = np.stack([f[mask].astype(float) for f in inits])
-    u = eng.upload_packed(u_host)
-    diffuser = (S._Diffuser(eng, M, a["dt"], rem, a["diffusion_scheme"], a["cn_rtol"],
-                            dcoef=[float(k["diffusion_coefficient"]) for k in kws]) if a["enable_diffusion"] else None)
-    times = [0.0]
-    frames = [[S.reconstruct_field(mask, u_host[m])] for m in range(M)]
-    mass = [[float(np.sum(u_host[m]) * dx * dx)] for m in range(M)]
-    for m, k in enumerate(kws):
-        S._notify(k["progress_callback"], 0.0, frames[m][0])
-    lazy = S._LazyOutputs()
-    want_now = any(k["progress_callback"] is not None for k in kws)
-    t = 0.0
-    done = 0
-    for step in range(1, total_steps + 1):
-        t += rem if step > full_steps else a["dt"]
-        if stored(step):
-            if diffuser is not None:
-                diffuser.advance(u, done + 1, step, full_steps)
-            done = step
-            times.append(float(t))
-            kk = len(frames[0])
-            for m in range(M):
-                frames[m].append(None)
-                mass[m].append(None)
-
-            def put(arr, kk=kk):
-                for m in range(M):
-                    frames[m][kk] = arr[m]
-                    mass[m][kk] = float(np.sum(arr[m][mask]) * dx * dx)
-
-            ticket = _frames_async(eng, u, mask)
-            if want_now:
-                put(ticket.result())
-                for m, k in enumerate(kws):
-                    S._notify(k["progress_callback"], t, frames[m][kk])
-            else:
-                lazy.add(ticket, put)
-    lazy.flush()
-    out = []
-    for m, k in enumerate(kws):
-        ph = k["phonon_history_out"]
-        if ph is not None:
-            f, ef, bins, meta = S.build_fixed_phonon_history(mask=mask, times=times, bath_temperature=k["bath_temperature"],
-                                                             phonon_energy_bins=None)
-            ph.update({"phonon_frames": f, "phonon_energy_frames": ef, "phonon_energy_bins": bins, "phonon_metadata": meta})
-        out.append((list(times), frames[m], mass[m], S._color_limits(frames[m]), None, None))
-    return out
+        return S._run_scalar(eng, sched, out, inits, [k["diffusion_coefficient"] for k in kws], a["enable_diffusion"],
+                             [k["bath_temperature"] for k in kws], [k["phonon_history_out"] for k in kws],
+                             a["diffusion_scheme"], a["cn_rtol"])
+    return _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, [(c[4], c[5]) for c in checked])
 
 
 def table_parameters(kws: list[dict], taus: list[tuple]) -> list[tuple]:
@@ -306,52 +247,96 @@ def table_parameters(kws: list[dict], taus: list[tuple]) -> list[tuple]:
     return out
 
 
-def _run_energy_batch(eng, kws, ids, errors, inits, mask, n, flags, taus, rem, full_steps, total_steps, stored):
-    """Energy-resolved mode for M members: the time loop of ``run_2d_crank_nicolson`` over [bin][member][cell] planes."""
-    a, M = kws[0], len(kws)
+class _MembersRun(EnergyRun):
+    """M problems over planes [bin][member][cell], driven by the ``*_members`` library calls: the guard is reduced per member
+    and every member warns / fails for itself.  ``ctab``, ``floor``, ``physics`` = (recombination, scattering, phonon
+    update), ``flags``, ``generations``, ``ids``, ``errors``, ``verdict`` and ``quiet_below`` are set by the caller."""
+
+    def __init__(self, *args):
+        super().__init__(*args)
+        self.members = self.out.members
+        self.warned = [False] * self.members
+        self.failed: list = [None] * self.members
+
+    def generate(self, t: float, dt_step: float) -> None:
+        gens, eng, M = self.generations, self.eng, self.members
+        if not any(g.active for g in gens):
+            return
+        amounts = generation_amounts([g.spec for g in gens], t, dt_step)
+        if any(x is None for x in amounts):                      # custom expressions: evaluated on the host
+            n = int(np.sum(self.out.mask))
+            g = np.zeros((self.state.shape[0] // M, M, n))
+            for m, x in enumerate(amounts):
+                g_ext = gens[m].rates(t) if x is None else None
+                if g_ext is not None:
+                    g[:, m] = g_ext
+            eng.add_scaled(self.state, eng.upload_packed(g.reshape(-1, n)), dt_step)
+        consts = [0.0 if x is None else x for x in amounts]
+        if any(g.constant for g in gens) or any(x != 0.0 for x in consts):
+            eng.add_constant_members(self.state, consts, eng.ncell, M, self.flags)
+
+    def pair_amount(self, t_next: float, dt_next: float):
+        # one scalar generation amount inside the pair kernel: only when every member adds the same
+        nxt = generation_amounts([g.spec for g in self.generations], t_next, dt_next)
+        return nxt[0] if all(x is not None and x == nxt[0] for x in nxt) else None
+
+    def collide(self, dt_col: float, guarded: bool):
+        eng = self.eng
+        if not guarded:
+            return eng.collide(self.ctab, self.state, self.state_alt, self.phonon, self.dE, dt_col, *self.physics,
+                               ncell=self.ncell, flags=self.flags)
+        _STATS["guarded_calls"] += 1
+        return eng.collide_guarded_members(self.ctab, self.state, self.state_alt, self.phonon, self.dE, dt_col,
+                                           *self.physics, self.floor, eng.ncell, self.members, self.flags)
+
+    def collide_pair(self, dt_a: float, dt_b: float, amount: float):
+        _STATS["pair_passes"] += 1
+        return self.eng.collide_pair_guarded_members(self.ctab, self.state, self.state_alt, self.phonon, self.dE, dt_a, dt_b,
+                                                     amount, *self.physics, self.floor, self.eng.ncell, self.members,
+                                                     self.flags)
+
+    def guard_launch(self):
+        return self.eng.pauli_stats_members_launch(self.state, self.ctab, self.floor, self.eng.ncell, self.members,
+                                                   self.flags)
+
+    def guard_check(self, ticket, step: int, t: float) -> None:
+        for m, stats in enumerate(self.eng.pauli_stats_members_result(ticket)):
+            # no forbidden density and no occupation above the lower threshold: the member has nothing to report
+            if self.failed[m] is not None or (stats[2] is None and not stats[0] > self.quiet_below):
+                continue
+            error, warning, self.warned[m] = self.verdict(stats, step, t, self.warned[m])
+            if error is not None:
+                self.failed[m] = ValueError(f"member {self.ids[m]}: {error}")
+                self.failed[m].step = step
+                if self.errors == "raise":
+                    raise self.failed[m]
+            elif warning is not None:
+                # guard_check <- guard_flush <- energy_loop <- _run_energy_batch <- _run_batch_on_device <- _run_batch <-
+                # run_2d_crank_nicolson_ensemble <- the caller
+                warnings.warn(f"member {self.ids[m]}: {warning}", stacklevel=8)
+
+
+def _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, taus):
+    """Energy-resolved mode for M members: the setup of ``run_2d_crank_nicolson`` over [bin][member][cell] planes."""
+    a, M, mask = kws[0], len(kws), out.mask
     tau_s_eff, tau_r_eff = taus[0]
     tparams = table_parameters(kws, taus)
     if all(p == tparams[0] for p in tparams):                    # one table set serves every member (no sweep, or all equal)
         tparams = None
-    lib, ncm = eng.lib, eng.ncell
-    dt, dx = a["dt"], a["dx"]
+    ncm = eng.ncell
     gap, NE = a["energy_gap"], a["num_energy_bins"]
     E_bins, dE = S.build_energy_grid(gap, a["energy_min_factor"], a["energy_max_factor"], NE)
-    precomputed = a["precomputed"]
-    if precomputed is None and a["gap_expression"].strip():      # one value of D and T_b (member_arguments checked)
-        from .models import SimulationParameters
-        from .precompute import precompute_arrays
-        params = SimulationParameters(
-            diffusion_coefficient=a["diffusion_coefficient"], dt=dt, total_time=a["total_time"], mesh_size=dx,
-            energy_gap=gap, energy_min_factor=a["energy_min_factor"], energy_max_factor=a["energy_max_factor"],
-            num_energy_bins=NE, dynes_gamma=a["dynes_gamma"], gap_expression=a["gap_expression"], tau_0=a["tau_0"],
-            tau_s=tau_s_eff, tau_r=tau_r_eff, T_c=a["T_c"], bath_temperature=a["bath_temperature"])
-        precomputed = precompute_arrays(mask, a["edges"], a["edge_conditions"], params, include_collision_kernels=False)
-    has_pre = precomputed is not None
-    nonuniform = has_pre and not bool(precomputed.get("is_uniform", True))
+    precomputed = S._auto_precomputed(                           # one value of D and T_b (member_arguments checked)
+        a["precomputed"], a["gap_expression"], mask, a["edges"], a["edge_conditions"],
+        diffusion_coefficient=a["diffusion_coefficient"], dt=a["dt"], total_time=a["total_time"], mesh_size=a["dx"],
+        energy_gap=gap, energy_min_factor=a["energy_min_factor"], energy_max_factor=a["energy_max_factor"],
+        num_energy_bins=NE, dynes_gamma=a["dynes_gamma"], tau_0=a["tau_0"], tau_s=tau_s_eff, tau_r=tau_r_eff, T_c=a["T_c"],
+        bath_temperature=a["bath_temperature"])
+    nonuniform = precomputed is not None and not bool(precomputed.get("is_uniform", True))
     S.normalize_collision_solver_name(a["collision_solver"])
     en_r, en_s = a["enable_recombination"], a["enable_scattering"]
-    upd = not a["freeze_phonon_dynamics"]
-    floor = a["pauli_density_floor"]
-
-    diffuser = None
-    if a["enable_diffusion"]:
-        scheme, rtol = a["diffusion_scheme"], a["cn_rtol"]
-        if has_pre:
-            D_array = np.asarray(precomputed["D_array"], dtype=float)
-        if nonuniform:                                           # field i * M + m is bin i of member m
-            dfield = np.zeros((NE, ncm))
-            dfield[:, eng.mask_flat] = D_array
-            diffuser = S._Diffuser(eng, NE * M, dt, rem, scheme, rtol, dfield=np.repeat(dfield, M, axis=0))
-        else:
-            per_member = []
-            for k in kws:
-                if has_pre:
-                    per_member.append([float(D_array[i, 0]) if D_array.ndim == 2 else float(D_array[i]) for i in range(NE)])
-                else:
-                    per_member.append([float(v) for v in _tb.diffusion_coefficients(E_bins, gap, k["diffusion_coefficient"])])
-            diffuser = S._Diffuser(eng, NE * M, dt, rem, scheme, rtol,
-                                   dcoef=[per_member[m][i] for i in range(NE) for m in range(M)])
+    diffuser = (S._energy_diffuser(eng, sched, a["diffusion_scheme"], a["cn_rtol"], E_bins, gap, precomputed,
+                                   [k["diffusion_coefficient"] for k in kws]) if a["enable_diffusion"] else None)
 
     omega_bins, idx_diff, idx_sum, diff_sign = S._build_phonon_frequency_map(E_bins)
     nw = omega_bins.size
@@ -364,218 +349,31 @@ def _run_energy_batch(eng, kws, ids, errors, inits, mask, n, flags, taus, rem, f
                                      k["energy_weights"], k["initial_condition_spec"]) for m, k in enumerate(kws)],
                           axis=1).reshape(NE * M, n)
     state = eng.upload_packed(state_host)                        # [NE * M, ncell] = [NE][M * ncell]
-    state_alt = eng.empty(NE * M, ncm)
-    phonon = eng.upload_packed(phonon_host)
-    coords = np.argwhere(mask)
-    cell_to_px = np.cumsum(eng.mask_flat) - 1
-    warned = [False] * M
-    failed: list = [None] * M
-    pending_guard: list = []
-
-    # a member whose step shows no forbidden density and no occupation above the lower threshold has nothing to report
-    quiet_below = min([v for v in (a["pauli_warn_threshold"], a["pauli_error_threshold"]) if v is not None],
-                      default=float("inf"))
-
-    def check(step_idx, time_ns, stats) -> None:
-        for m in range(M):
-            if failed[m] is not None or (stats[m][2] is None and not stats[m][0] > quiet_below):
-                continue
-            error, warning, warned[m] = S._pauli_verdict(stats[m], step_idx, time_ns, E_bins, coords, cell_to_px, warned[m],
-                                                         a["enforce_pauli"], a["pauli_warn_threshold"],
-                                                         a["pauli_error_threshold"])
-            if error is not None:
-                failed[m] = ValueError(f"member {ids[m]}: {error}")
-                failed[m].step = step_idx
-                if errors == "raise":
-                    raise failed[m]
-            elif warning is not None:
-                warnings.warn(f"member {ids[m]}: {warning}", stacklevel=4)
-
-    def guard_launch(step_idx, time_ns) -> None:
-        pending_guard.append((eng.pauli_stats_members_launch(state, ctab, floor, ncm, M, flags), step_idx, time_ns))
-
-    def guard_flush(keep: int = 0) -> None:
-        while len(pending_guard) > keep:
-            ticket, step_idx, time_ns = pending_guard.pop(0)
-            check(step_idx, time_ns, eng.pauli_stats_members_result(ticket))
-
-    check(0, 0.0, eng.pauli_stats_members_result(eng.pauli_stats_members_launch(state, ctab, floor, ncm, M, flags)))
-
-    want_ph = [k["phonon_history_out"] is not None for k in kws]
-    ph_frames = [[] for _ in range(M)]
-    ph_eframes = [[] for _ in range(M)]
-    ph_w = (eng.torch.as_tensor(S.integration_widths_from_centers(omega_bins, fallback_width=dE), device=eng.device)
-            if any(want_ph) else None)
-    callbacks = [k["progress_callback"] for k in kws]
-    lazy = S._LazyOutputs()
-
-    def per_member_planes(arr, nplanes):
-        arr = arr.reshape((nplanes, M) + arr.shape[1:])
-        return [list(np.ascontiguousarray(arr[:, m])) for m in range(M)]
-
-    def snapshot_phonons() -> None:
-        kk = len(ph_frames[0])
-        for m in range(M):
-            ph_eframes[m].append(None)
-            ph_frames[m].append(None)
-
-        def put_e(arr, kk=kk):
-            for m, planes in enumerate(per_member_planes(arr, nw)):
-                ph_eframes[m][kk] = planes
-
-        def put_sum(arr, kk=kk):
-            for m in range(M):
-                ph_frames[m][kk] = arr[m]
-
-        lazy.add(_frames_async(eng, phonon, mask), put_e)
-        summed = eng.empty(M * ncm)
-        _hip.check(lib.qp_weighted_sum(_ptr(phonon), _ptr(ph_w), nw, M * ncm, _ptr(summed), eng.stream),
-                     "qp_weighted_sum")
-        lazy.add(_frames_async(eng, summed, mask), put_sum)
-
-    times: list[float] = [0.0]
-    frames = [[] for _ in range(M)]
-    energy_frames = [[] for _ in range(M)]
-    mass = [[] for _ in range(M)]
-
-    def store(t_now: float) -> None:
-        kk = len(frames[0])
-        for m in range(M):
-            frames[m].append(None)
-            energy_frames[m].append(None)
-            mass[m].append(None)
-        integ = eng.empty(M * ncm)
-        _hip.check(lib.qp_energy_integrate(_ptr(state), NE, M * ncm, float(dE), _ptr(integ), eng.stream),
-                     "qp_energy_integrate")
-        t_int = _frames_async(eng, integ, mask)
-
-        def put_integrated(arr, kk=kk):
-            for m in range(M):
-                frames[m][kk] = arr[m]
-                mass[m][kk] = float(np.sum(arr[m][mask]) * dx * dx)
-
-        def put_energy(arr, kk=kk):
-            for m, planes in enumerate(per_member_planes(arr, NE)):
-                energy_frames[m][kk] = planes
-
-        lazy.add(_frames_async(eng, state, mask), put_energy)
-        if any(want_ph):
-            snapshot_phonons()
-        if any(cb is not None for cb in callbacks):
-            put_integrated(t_int.result())
-            for m, cb in enumerate(callbacks):
-                S._notify(cb, t_now, frames[m][kk])
-        else:
-            lazy.add(t_int, put_integrated)
-
-    store(0.0)
+    histories = [k["phonon_history_out"] for k in kws]
+    run = _MembersRun(eng, out, state, eng.empty(NE * M, ncm), eng.upload_packed(phonon_host), dE,
+                      S._phonon_widths(eng, omega_bins, dE, histories))
+    run.ctab, run.floor, run.physics = ctab, a["pauli_density_floor"], (en_r, en_s, not a["freeze_phonon_dynamics"])
+    run.flags, run.generations = flags, [S._Generation(k["external_generation"], mask, E_bins) for k in kws]
+    run.ids, run.errors = ids, errors
+    run.verdict = S._guard_rule(eng, mask, E_bins, a["enforce_pauli"], a["pauli_warn_threshold"], a["pauli_error_threshold"])
+    run.quiet_below = min([v for v in (a["pauli_warn_threshold"], a["pauli_error_threshold"]) if v is not None],
+                          default=float("inf"))
 
     collisions = bool(en_r or en_s)
-    specs = [k["external_generation"] for k in kws]
-    gen_active = [spec is not None and spec.mode != "none" for spec in specs]
-    constant_mode = [g and spec.mode.strip().lower() == "constant" for g, spec in zip(gen_active, specs)]
-    compiled: list = [None] * M
+    energy_loop(run, sched, diffuser, collisions=collisions,
+                pair_ok=bool(collisions and a["enable_diffusion"] and Engine.pair_members_supported(ctab, ncm, M)),
+                batch_diffusion=S._one_call_diffusion(diffuser, collisions, any(g.active for g in run.generations),
+                                                      a["pauli_warn_threshold"], a["pauli_error_threshold"], rho_tab),
+                guard_lag=eng.GUARD_LAG)
 
-    def collide(dt_col, guard_step=None) -> bool:
-        nonlocal state, state_alt
-        if dt_col <= 0.0 or not collisions:
-            return False
-        if guard_step is None:
-            eng.collide(ctab, state, state_alt, phonon, dE, dt_col, en_r, en_s, upd, ncell=M * ncm, flags=flags)
-        else:
-            ticket = eng.collide_guarded_members(ctab, state, state_alt, phonon, dE, dt_col, en_r, en_s, upd, floor, ncm, M,
-                                                 flags)
-            pending_guard.append((ticket, guard_step[0], guard_step[1]))
-            _STATS["guarded_calls"] += 1
-        state, state_alt = state_alt, state
-        return guard_step is not None
-
-    def generate(t_start, dt_step) -> None:
-        amounts = generation_amounts(specs, t_start, dt_step)
-        if any(x is None for x in amounts):                      # custom expressions: evaluated on the host
-            g = np.zeros((NE, M, n))
-            for m, x in enumerate(amounts):
-                if x is None:
-                    if compiled[m] is None:
-                        compiled[m] = S._CustomGeneration(specs[m], mask)
-                    g_ext = S.evaluate_external_generation(specs[m], E_bins, n, t_start, mask, _compiled=compiled[m])
-                    if g_ext is not None:
-                        g[:, m] = g_ext
-            eng.add_scaled(state, eng.upload_packed(g.reshape(NE * M, n)), dt_step)
-        consts = [0.0 if x is None else x for x in amounts]
-        if any(constant_mode) or any(x != 0.0 for x in consts):
-            eng.add_constant_members(state, consts, ncm, M, flags)
-
-    batch_diffusion = (a["enable_diffusion"] and not collisions and not any(gen_active) and a["diffusion_scheme"] == "adi"
-                       and a["pauli_error_threshold"] is None and a["pauli_warn_threshold"] is None
-                       and float(np.min(rho_tab)) > 1e-30)
-    pair_ok = bool(collisions and a["enable_diffusion"] and Engine.pair_members_supported(ctab, ncm, M))
-    current_time = 0.0
-    done = 0
-    opened = False
-    for step in range(1, total_steps + 1):                       # the lone loop, solver.run_2d_crank_nicolson
-        final = step > full_steps
-        dt_step = rem if final else dt
-        if batch_diffusion:
-            current_time += dt_step
-            if stored(step):
-                diffuser.advance(state, done + 1, step, full_steps)
-                done = step
-                times.append(float(current_time))
-                store(current_time)
+    results = []
+    for m, history in enumerate(histories):
+        if run.failed[m] is not None:
+            results.append(run.failed[m])
             continue
-        if any(gen_active) and not opened:
-            generate(current_time, dt_step)
-        guarded = False
-        if collisions and a["enable_diffusion"]:                 # Strang: C(dt/2) D(dt) C(dt/2)
-            if not opened:
-                collide(0.5 * dt_step)
-            opened = False
-            diffuser.step(state, final)
-            nxt = None
-            if pair_ok and step < total_steps and not stored(step) and dt_step > 0.0:
-                dt_next = rem if step + 1 > full_steps else dt
-                nxt = generation_amounts(specs, current_time + dt_step, dt_next)
-                # one scalar generation amount inside the pair kernel: only when every member adds the same
-                nxt = nxt[0] if all(x is not None and x == nxt[0] for x in nxt) else None
-            if nxt is not None:
-                ticket = eng.collide_pair_guarded_members(ctab, state, state_alt, phonon, dE, 0.5 * dt_step, 0.5 * dt_next,
-                                                          nxt, en_r, en_s, upd, floor, ncm, M, flags)
-                pending_guard.append((ticket, step, current_time + dt_step))
-                _STATS["pair_passes"] += 1
-                state, state_alt = state_alt, state
-                guarded = opened = True
-            else:
-                guarded = collide(0.5 * dt_step, guard_step=(step, current_time + dt_step))
-        else:
-            diffuse_after = a["enable_diffusion"] and dt_step > 0.0
-            guarded = collide(dt_step, guard_step=None if diffuse_after else (step, current_time + dt_step))
-            if diffuse_after:
-                diffuser.step(state, final)
-        if not guarded:
-            guard_launch(step, current_time + dt_step)
-        guard_flush(keep=0 if stored(step) else eng.GUARD_LAG)
-        current_time += dt_step
-        if stored(step):
-            times.append(float(current_time))
-            store(current_time)
-    guard_flush()
-    lazy.flush()
-
-    out = []
-    for m, k in enumerate(kws):
-        if failed[m] is not None:
-            out.append(failed[m])
-            continue
-        ph = k["phonon_history_out"]
-        if ph is not None:
-            ph.clear()
-            ph.update({
-                "phonon_frames": ph_frames[m],
-                "phonon_energy_frames": ph_eframes[m],
-                "phonon_energy_bins": np.asarray(omega_bins, dtype=float).copy(),
-                "phonon_metadata": {"mode": "dynamic_local_coupled", "field_units": "integrated_occupation",
-                                    "energy_frame_units": "occupation"},
-            })
-        out.append((list(times), frames[m], mass[m], S._color_limits(frames[m]), energy_frames[m], E_bins.copy()))
-    return out
+        if history is not None:
+            history.clear()
+            history.update(S._dynamic_phonon_history(out, m, omega_bins))
+        results.append((list(out.times), out.frames[m], out.mass[m], S._color_limits(out.frames[m]), out.energy_frames[m],
+                        E_bins.copy()))
+    return results

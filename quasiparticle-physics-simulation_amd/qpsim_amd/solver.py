@@ -33,6 +33,7 @@ from .models import (
     normalize_collision_solver_name,
 )
 from .safe_eval import compile_safe_expression
+from .timeloop import EnergyRun, Outputs, Schedule, energy_loop, scalar_loop
 
 # names the reference exposes from qpsim.solver
 build_energy_grid = _tb.build_energy_grid
@@ -195,61 +196,12 @@ def _crop_to_bounding_box(mask: np.ndarray, edges: list[EdgeSegment]):
     return np.ascontiguousarray(mask[r0:r1, c0:c1]), shifted
 
 
-def _device_frames_async(eng, planes, mask: np.ndarray):
-    """Device planes -> ticket for host [n, ny, nx] frames on the FULL mask, NaN outside the interior (reconstruct_field
-    semantics).  Padding and, for a cropped engine grid, the embedding into the full frame are done on the device; the copy
-    to the host runs on a side stream into pinned memory while the time loop goes on (``ticket.result()`` waits for it)."""
-    if (eng.ny, eng.nx) == mask.shape:
-        return eng.download_frames_async(planes)
-    r0 = int(np.flatnonzero(mask.any(axis=1))[0])
-    c0 = int(np.flatnonzero(mask.any(axis=0))[0])
-    return eng.download_frames_async(planes, full_shape=mask.shape, offset=(r0, c0))
-
-
-def _device_frames(eng, planes, mask: np.ndarray) -> np.ndarray:
-    return _device_frames_async(eng, planes, mask).result()
-
-
-class _LazyOutputs:
-    """Store points enqueue their downloads and go on; the host arrays are filled in when the copies have landed (when a
-    staging slot is recycled, when a progress callback needs the frame, or before the run returns)."""
-
-    def __init__(self):
-        self._pending: list = []
-
-    def add(self, ticket, consume) -> None:
-        self._pending.append((ticket, consume))
-
-    def flush(self) -> None:
-        while self._pending:
-            ticket, consume = self._pending.pop(0)
-            consume(ticket.result())
-
-
-def _step_plan(total_time: float, dt: float) -> tuple[int, float, int]:
-    """(full steps, remainder dt or 0, total steps) (solver.py:1085-1089)."""
-    full = int(np.floor(total_time / dt + 1e-12))
-    rem = float(total_time - full * dt)
-    if rem < 1e-12:
-        rem = 0.0
-    return full, rem, full + (1 if rem > 0.0 else 0)
-
-
 def _color_limits(frames: list[np.ndarray]) -> list[float]:
     stack = np.stack(frames)
     lo, hi = float(np.nanmin(stack)), float(np.nanmax(stack))
     if abs(hi - lo) < 1e-12:
         hi = lo + 1e-9
     return [lo, hi]
-
-
-def _notify(cb, t: float, frame: np.ndarray) -> None:
-    if cb is None:
-        return
-    try:
-        cb(float(t), np.array(frame, copy=True))
-    except Exception:
-        pass
 
 
 class _Diffuser:
@@ -539,46 +491,28 @@ def run_2d_crank_nicolson(
     # mask whose interior is a solid rectangle inside a padded frame (the reference's built-in geometry) thereby
     # becomes a full rectangle on the device and takes the tiled ADI path.
     geom = _run_geometry(mask, edges, edge_conditions, dx, enable_diffusion)
-    full_steps, rem, total_steps = _step_plan(total_time, dt)
+    sched = Schedule(total_time, dt, store_every)
     eng = Engine(geom, device=device)
     eng.pin_stream()          # one stream for the whole run: skip the per-launch lookup
-    stored = lambda step: step % store_every == 0 or step == total_steps  # noqa: E731
+    out = Outputs(mask, dx, [progress_callback])
 
     if not energy_gap > 0.0:
-        return _run_scalar(eng, mask, initial_field, diffusion_coefficient, dt, rem, full_steps, total_steps, dx,
-                           stored, enable_diffusion, bath_temperature, phonon_history_out, progress_callback,
-                           diffusion_scheme, cn_rtol)
+        return _run_scalar(eng, sched, out, [initial_field], [diffusion_coefficient], enable_diffusion, [bath_temperature],
+                           [phonon_history_out], diffusion_scheme, cn_rtol)[0]
 
     # ------------------------------------------------------------------ energy-resolved mode
     gap = energy_gap
     NE = num_energy_bins
     E_bins, dE = build_energy_grid(gap, energy_min_factor, energy_max_factor, NE)
-    if precomputed is None and gap_expression.strip():          # auto-precompute (solver.py:1106-1124)
-        from .precompute import precompute_arrays
-        params = SimulationParameters(
-            diffusion_coefficient=diffusion_coefficient, dt=dt, total_time=total_time, mesh_size=dx,
-            energy_gap=energy_gap, energy_min_factor=energy_min_factor, energy_max_factor=energy_max_factor,
-            num_energy_bins=num_energy_bins, dynes_gamma=dynes_gamma, gap_expression=gap_expression, tau_0=tau_0,
-            tau_s=tau_s_eff, tau_r=tau_r_eff, T_c=T_c, bath_temperature=bath_temperature)
-        precomputed = precompute_arrays(mask, edges, edge_conditions, params, include_collision_kernels=False)
-    has_pre = precomputed is not None
-    nonuniform = has_pre and not bool(precomputed.get("is_uniform", True))
+    precomputed = _auto_precomputed(
+        precomputed, gap_expression, mask, edges, edge_conditions, diffusion_coefficient=diffusion_coefficient, dt=dt,
+        total_time=total_time, mesh_size=dx, energy_gap=energy_gap, energy_min_factor=energy_min_factor,
+        energy_max_factor=energy_max_factor, num_energy_bins=num_energy_bins, dynes_gamma=dynes_gamma, tau_0=tau_0,
+        tau_s=tau_s_eff, tau_r=tau_r_eff, T_c=T_c, bath_temperature=bath_temperature)
+    nonuniform = precomputed is not None and not bool(precomputed.get("is_uniform", True))
     normalize_collision_solver_name(collision_solver)
-
-    if has_pre:
-        D_array = np.asarray(precomputed["D_array"], dtype=float)
-    else:
-        D_array = _tb.diffusion_coefficients(E_bins, gap, diffusion_coefficient)[:, None] * np.ones((1, n))
-
-    diffuser = None
-    if enable_diffusion:
-        if nonuniform:                                           # variable D(x) per bin (solver.py:1145-1164)
-            dfield = np.zeros((NE, eng.ncell))
-            dfield[:, eng.mask_flat] = D_array
-            diffuser = _Diffuser(eng, NE, dt, rem, diffusion_scheme, cn_rtol, dfield=dfield)
-        else:                                                    # one scalar D per bin (solver.py:1166-1174)
-            dcoef = [float(D_array[i, 0]) if D_array.ndim == 2 else float(D_array[i]) for i in range(NE)]
-            diffuser = _Diffuser(eng, NE, dt, rem, diffusion_scheme, cn_rtol, dcoef=dcoef)
+    diffuser = (_energy_diffuser(eng, sched, diffusion_scheme, cn_rtol, E_bins, gap, precomputed, [diffusion_coefficient])
+                if enable_diffusion else None)
 
     # collision tables (solver.py:1189-1238): phonon grid, thermal phonons, per-gap-class kernels
     omega_bins, idx_diff, idx_sum, diff_sign = _build_phonon_frequency_map(E_bins)
@@ -589,231 +523,164 @@ def run_2d_crank_nicolson(
     state_host = _initial_qp_state(mask, initial_field, E_bins, dE, gap, dynes_gamma, energy_weights,
                                    initial_condition_spec)
     state = eng.upload_packed(state_host)
-    state_alt = eng.empty(NE, eng.ncell)
-    phonon = eng.upload_packed(phonon_host)
-    coords = np.argwhere(mask)
-    cell_to_px = np.cumsum(eng.mask_flat) - 1
+    run = _LoneRun(eng, out, state, eng.empty(NE, eng.ncell), eng.upload_packed(phonon_host), dE,
+                   _phonon_widths(eng, omega_bins, dE, [phonon_history_out]))
+    run.ctab, run.floor = ctab, pauli_density_floor
+    run.physics = (enable_recombination, enable_scattering, not freeze_phonon_dynamics)
+    run.generation = _Generation(external_generation, mask, E_bins)
+    run.verdict = _guard_rule(eng, mask, E_bins, enforce_pauli, pauli_warn_threshold, pauli_error_threshold)
+
+    collisions = bool(enable_recombination or enable_scattering)
+    energy_loop(run, sched, diffuser, collisions=collisions,
+                pair_ok=bool(collisions and enable_diffusion and ctab.get("pair")),
+                batch_diffusion=_one_call_diffusion(diffuser, collisions, run.generation.active, pauli_warn_threshold,
+                                                    pauli_error_threshold, rho_tab),
+                guard_lag=eng.GUARD_LAG)
+
+    if phonon_history_out is not None:
+        phonon_history_out.clear()
+        phonon_history_out.update(_dynamic_phonon_history(out, 0, omega_bins))
+    return out.times, out.frames[0], out.mass[0], _color_limits(out.frames[0]), out.energy_frames[0], E_bins
+
+
+class _LoneRun(EnergyRun):
+    """One problem, driven by the plain library calls (an ensemble of one would launch other kernels).  ``ctab``, ``floor``,
+    ``physics`` = (recombination, scattering, phonon update), ``generation`` and ``verdict`` are set by the caller."""
     warned = False
 
-    # The guard of step k is enqueued right after the step and examined after step k + GUARD_LAG has been enqueued (or
-    # before anything is stored / returned), so the device does not idle during the host round trip and the host never
-    # sleeps on an event.  Messages carry the step / time of the step that was checked, exactly as the reference's.
-    pending_guard: list = []
+    def generate(self, t: float, dt_step: float) -> None:
+        gen = self.generation
+        if not gen.active:
+            return
+        amount = gen.amount(t, dt_step)
+        if amount is None:                                       # custom mode: evaluated on the host (solver.py:918-962)
+            g_ext = gen.rates(t)
+            if g_ext is not None:
+                self.eng.add_scaled(self.state, self.eng.upload_packed(g_ext), dt_step)
+        elif gen.constant or amount != 0.0:
+            self.eng.add_constant(self.state, amount)
 
-    def guard_launch(step_idx: int, time_ns: float) -> None:
-        pending_guard.append((eng.pauli_stats_launch(state, ctab, pauli_density_floor), step_idx, time_ns))
+    def pair_amount(self, t_next: float, dt_next: float):
+        return self.generation.amount(t_next, dt_next)
 
-    def guard_flush(keep: int = 0) -> None:
-        while len(pending_guard) > keep:
-            ticket, step_idx, time_ns = pending_guard.pop(0)
-            guard(step_idx, time_ns, eng.pauli_stats_result(ticket))
+    def collide(self, dt_col: float, guarded: bool):
+        call = self.eng.collide_guarded if guarded else self.eng.collide
+        return call(self.ctab, self.state, self.state_alt, self.phonon, self.dE, dt_col, *self.physics,
+                    *((self.floor,) if guarded else ()))
 
-    def guard(step_idx: int, time_ns: float, stats=None) -> None:   # Pauli guard (solver.py:1296-1344)
-        nonlocal warned
-        if stats is None:
-            stats = eng.pauli_stats(state, ctab, pauli_density_floor)
-        error, warning, warned = _pauli_verdict(stats, step_idx, time_ns, E_bins, coords, cell_to_px, warned, enforce_pauli,
-                                                pauli_warn_threshold, pauli_error_threshold)
+    def collide_pair(self, dt_a: float, dt_b: float, amount: float):
+        return self.eng.collide_pair_guarded(self.ctab, self.state, self.state_alt, self.phonon, self.dE, dt_a, dt_b,
+                                             amount, *self.physics, self.floor)
+
+    def guard_launch(self):
+        return self.eng.pauli_stats_launch(self.state, self.ctab, self.floor)
+
+    def guard_check(self, ticket, step: int, t: float) -> None:  # Pauli guard (solver.py:1296-1344)
+        error, warning, self.warned = self.verdict(self.eng.pauli_stats_result(ticket), step, t, self.warned)
         if error is not None:
             raise ValueError(error)
         if warning is not None:
-            warnings.warn(warning, stacklevel=3)
+            # guard_check <- guard_flush <- energy_loop <- run_2d_crank_nicolson <- its device wrapper <- the caller
+            warnings.warn(warning, stacklevel=6)
 
-    guard(0, 0.0)
 
-    want_ph = phonon_history_out is not None
-    ph_frames: list[np.ndarray] = []
-    ph_eframes: list[list[np.ndarray]] = []
-    ph_widths = integration_widths_from_centers(omega_bins, fallback_width=dE) if want_ph else None
+class _Generation:
+    """External generation of one problem during a run; a custom expression is compiled at its first use."""
 
-    lazy = _LazyOutputs()
+    def __init__(self, spec, mask, E_bins):
+        self.spec, self.mask, self.E_bins = spec, mask, E_bins
+        # the reference gates on the raw mode string (solver.py:1459)
+        self.active = spec is not None and spec.mode != "none"
+        self.constant = self.active and spec.mode.strip().lower() == "constant"
+        self._compiled = None
 
-    def snapshot_phonons() -> None:                              # solver.py:1354-1360
-        k = len(ph_frames)
-        ph_eframes.append(None)
-        ph_frames.append(None)
-        lazy.add(_device_frames_async(eng, phonon, mask),        # NaN-padded on the device
-                 lambda arr, k=k: ph_eframes.__setitem__(k, list(arr)))
-        lazy.add(_device_frames_async(eng, eng.weighted_sum(phonon, ph_widths), mask),
-                 lambda arr, k=k: ph_frames.__setitem__(k, arr[0]))
+    def amount(self, t_start: float, dt_of_step: float):
+        return _generation_amount(self.spec, t_start, dt_of_step)
 
-    times: list[float] = [0.0]
-    frames: list[np.ndarray] = []
-    energy_frames: list[list[np.ndarray]] = []
-    mass: list[float] = []
+    def rates(self, t: float):
+        """g_ext of custom mode at ``t`` as [NE, n] on the host (solver.py:918-962)."""
+        if self._compiled is None:
+            self._compiled = _CustomGeneration(self.spec, self.mask)
+        return evaluate_external_generation(self.spec, self.E_bins, int(np.sum(self.mask)), t, self.mask,
+                                            _compiled=self._compiled)
 
-    def store():                                                 # solver.py:1367-1374, 1480-1489
-        # frames are formed on the device (energy integral, NaN padding), cross PCIe once on a side stream while the
-        # next steps run, and are handed out as they are; only a progress callback forces the integrated frame now
-        k = len(frames)
-        frames.append(None)
-        energy_frames.append(None)
-        mass.append(None)
-        t_int = _device_frames_async(eng, eng.energy_integral(state, dE), mask)
 
-        def put_integrated(arr, k=k):
-            frames[k] = arr[0]
-            mass[k] = float(np.sum(arr[0][mask]) * dx * dx)     # same summation order as the reference's packed sum
+def _auto_precomputed(precomputed, gap_expression: str, mask, edges, edge_conditions, **parameters):
+    """``precomputed`` as given, or built from ``gap_expression`` when there is one (solver.py:1106-1124)."""
+    if precomputed is None and gap_expression.strip():
+        from .precompute import precompute_arrays
+        params = SimulationParameters(gap_expression=gap_expression, **parameters)
+        precomputed = precompute_arrays(mask, edges, edge_conditions, params, include_collision_kernels=False)
+    return precomputed
 
-        lazy.add(_device_frames_async(eng, state, mask), lambda arr, k=k: energy_frames.__setitem__(k, list(arr)))
-        if want_ph:
-            snapshot_phonons()
-        if progress_callback is not None:
-            put_integrated(t_int.result())
-            return frames[k]
-        lazy.add(t_int, put_integrated)
+
+def _energy_diffuser(eng, sched, scheme, rtol, E_bins, gap, precomputed, coefficients) -> "_Diffuser":
+    """Diffusion of NE * M fields, field i * M + m being bin i of member m: ``precomputed["D_array"]`` when there is one (a
+    variable D(x) per bin if the gap is not uniform, solver.py:1145-1164), else D(E) of each member's coefficient
+    (solver.py:1166-1174)."""
+    NE, M = len(E_bins), len(coefficients)
+    if precomputed is None:
+        per_member = [[float(v) for v in _tb.diffusion_coefficients(E_bins, gap, D)] for D in coefficients]
+    else:
+        D_array = np.asarray(precomputed["D_array"], dtype=float)
+        if not bool(precomputed.get("is_uniform", True)):
+            dfield = np.zeros((NE, eng.ncell))
+            dfield[:, eng.mask_flat] = D_array
+            return _Diffuser(eng, NE * M, sched.dt, sched.rem, scheme, rtol, dfield=np.repeat(dfield, M, axis=0))
+        per_member = [[float(D_array[i, 0]) if D_array.ndim == 2 else float(D_array[i]) for i in range(NE)]] * M
+    return _Diffuser(eng, NE * M, sched.dt, sched.rem, scheme, rtol,
+                     dcoef=[per_member[m][i] for i in range(NE) for m in range(M)])
+
+
+def _one_call_diffusion(diffuser, collisions: bool, generation: bool, warn_threshold, error_threshold, rho_tab) -> bool:
+    """Pure diffusion (no collisions, no generation) with a guard that cannot fire (no thresholds, no forbidden bins):
+    nothing but diffusion steps lies between two store points, so the stretch is one call as in scalar mode."""
+    return bool(diffuser is not None and not collisions and not generation and diffuser.scheme == "adi"
+                and error_threshold is None and warn_threshold is None and float(np.min(rho_tab)) > 1e-30)
+
+
+def _guard_rule(eng, mask, E_bins, enforce_pauli, warn_threshold, error_threshold):
+    """``_pauli_verdict`` of one run as ``rule(stats, step, time, warned)``."""
+    coords = np.argwhere(mask)
+    cell_to_px = np.cumsum(eng.mask_flat) - 1
+    return lambda stats, step, t, warned: _pauli_verdict(stats, step, t, E_bins, coords, cell_to_px, warned, enforce_pauli,
+                                                         warn_threshold, error_threshold)
+
+
+def _phonon_widths(eng, omega_bins, dE, histories):
+    """Integration widths of the phonon grid on the device when any member wants phonon frames, else None."""
+    if all(h is None for h in histories):
         return None
+    return eng.upload_vector(integration_widths_from_centers(omega_bins, fallback_width=dE))
 
-    _notify(progress_callback, 0.0, store())
 
-    collisions = bool(enable_recombination or enable_scattering)
-    gen_mode = "none" if external_generation is None else external_generation.mode.strip().lower()
-    # the reference gates on the raw mode string (solver.py:1459)
-    gen_active = external_generation is not None and external_generation.mode != "none"
-
-    def collide(dt_col: float, guard_step=None):
-        """One collision update; with ``guard_step = (step, time)`` the Pauli guard of that step is reduced by the same
-        library call (the collision is then the last operation of the step).  Returns True when the guard was enqueued."""
-        nonlocal state, state_alt
-        if dt_col <= 0.0 or not collisions:
-            return False
-        if guard_step is None:
-            eng.collide(ctab, state, state_alt, phonon, dE, dt_col, enable_recombination, enable_scattering,
-                        not freeze_phonon_dynamics)
-        else:
-            ticket = eng.collide_guarded(ctab, state, state_alt, phonon, dE, dt_col, enable_recombination,
-                                         enable_scattering, not freeze_phonon_dynamics, pauli_density_floor)
-            pending_guard.append((ticket, guard_step[0], guard_step[1]))
-        state, state_alt = state_alt, state
-        return guard_step is not None
-
-    # Pure diffusion (no collisions, no generation) with a guard that cannot fire (no thresholds, no forbidden bins):
-    # nothing but diffusion steps lies between two store points, so the stretch is one call as in scalar mode.
-    batch_diffusion = (enable_diffusion and not collisions and not gen_active and diffusion_scheme == "adi"
-                       and pauli_error_threshold is None and pauli_warn_threshold is None
-                       and float(np.min(rho_tab)) > 1e-30)
-    def generation_amount(t_start: float, dt_of_step: float):
-        return _generation_amount(external_generation, t_start, dt_of_step)
-
-    current_time = 0.0
-    done = 0
-    custom_generation = None                                     # compiled at its first use, then reused every step
-    # Strang steps that follow one another without a store point in between: the closing half-step of step k and the
-    # opening half-step of step k + 1 run as ONE pass over the state (Engine.collide_pair_guarded) - `opened` says that
-    # the generation term and the first half-step of the step now starting were already applied by that pass.
-    pair_ok = bool(collisions and enable_diffusion and ctab.get("pair"))
-    opened = False
-    for step in range(1, total_steps + 1):                       # solver.py:1454-1494
-        final = step > full_steps
-        dt_step = rem if final else dt
-        if batch_diffusion:
-            current_time += dt_step
-            if stored(step):
-                diffuser.advance(state, done + 1, step, full_steps)
-                done = step
-                times.append(float(current_time))
-                _notify(progress_callback, current_time, store())
-            continue
-        if gen_active and not opened:
-            amount = generation_amount(current_time, dt_step)
-            if amount is None:                                   # custom mode: evaluated on the host (solver.py:918-962)
-                if custom_generation is None:
-                    custom_generation = _CustomGeneration(external_generation, mask)
-                g_ext = evaluate_external_generation(external_generation, E_bins, n, current_time, mask,
-                                                     _compiled=custom_generation)
-                if g_ext is not None:
-                    eng.add_scaled(state, eng.upload_packed(g_ext), dt_step)
-            elif gen_mode == "constant" or amount != 0.0:
-                eng.add_constant(state, amount)
-        guarded = False
-        if collisions and enable_diffusion:                      # Strang: C(dt/2) D(dt) C(dt/2)
-            if not opened:
-                collide(0.5 * dt_step)
-            opened = False
-            diffuser.step(state, final)
-            nxt_amount = None
-            if pair_ok and step < total_steps and not stored(step) and dt_step > 0.0:
-                dt_next = rem if step + 1 > full_steps else dt
-                nxt_amount = generation_amount(current_time + dt_step, dt_next)
-            if nxt_amount is not None:
-                ticket = eng.collide_pair_guarded(ctab, state, state_alt, phonon, dE, 0.5 * dt_step, 0.5 * dt_next,
-                                                  nxt_amount, enable_recombination, enable_scattering,
-                                                  not freeze_phonon_dynamics, pauli_density_floor)
-                pending_guard.append((ticket, step, current_time + dt_step))
-                state, state_alt = state_alt, state
-                guarded = opened = True
-            else:
-                guarded = collide(0.5 * dt_step, guard_step=(step, current_time + dt_step))
-        else:
-            diffuse_after = enable_diffusion and dt_step > 0.0
-            guarded = collide(dt_step, guard_step=None if diffuse_after else (step, current_time + dt_step))
-            if diffuse_after:
-                diffuser.step(state, final)
-        if not guarded:
-            guard_launch(step, current_time + dt_step)
-        guard_flush(keep=0 if stored(step) else eng.GUARD_LAG)
-        current_time += dt_step
-        if stored(step):
-            times.append(float(current_time))
-            _notify(progress_callback, current_time, store())
-    guard_flush()
-    lazy.flush()
-
-    limits = _color_limits(frames)
-    if phonon_history_out is not None:
-        phonon_history_out.clear()
-        phonon_history_out.update({
-            "phonon_frames": ph_frames,
-            "phonon_energy_frames": ph_eframes,
+def _dynamic_phonon_history(out: Outputs, m: int, omega_bins) -> dict:
+    return {"phonon_frames": out.phonon_frames[m],
+            "phonon_energy_frames": out.phonon_energy_frames[m],
             "phonon_energy_bins": np.asarray(omega_bins, dtype=float).copy(),
             "phonon_metadata": {"mode": "dynamic_local_coupled", "field_units": "integrated_occupation",
-                                "energy_frame_units": "occupation"},
-        })
-    return times, frames, mass, limits, energy_frames, E_bins
+                                "energy_frame_units": "occupation"}}
 
 
-def _run_scalar(eng: Engine, mask, initial_field, D, dt, rem, full_steps, total_steps, dx, stored, enable_diffusion,
-                bath_temperature, phonon_history_out, progress_callback, scheme, rtol):
-    """Legacy scalar mode, energy_gap == 0 (solver.py:1517-1587)."""
-    u_host = initial_field[mask].astype(float)
-    u = eng.upload_packed(u_host[None, :])
-    diffuser = _Diffuser(eng, 1, dt, rem, scheme, rtol, dcoef=[float(D)]) if enable_diffusion else None
-    times = [0.0]
-    frames = [reconstruct_field(mask, u_host)]
-    mass = [float(np.sum(u_host) * dx * dx)]
-    _notify(progress_callback, 0.0, frames[0])
-    lazy = _LazyOutputs()
-    t = 0.0
-    done = 0
-    for step in range(1, total_steps + 1):
-        t += rem if step > full_steps else dt          # same accumulation order as the reference
-        if stored(step):
-            if diffuser is not None:                   # nothing happens between two store points but diffusion steps
-                diffuser.advance(u, done + 1, step, full_steps)
-            done = step
-            times.append(float(t))
-            k = len(frames)
-            frames.append(None)
-            mass.append(None)
-
-            def put(arr, k=k):
-                frames[k] = arr[0]
-                mass[k] = float(np.sum(arr[0][mask]) * dx * dx)
-
-            ticket = _device_frames_async(eng, u, mask)
-            if progress_callback is not None:
-                put(ticket.result())
-                _notify(progress_callback, t, frames[k])
-            else:
-                lazy.add(ticket, put)
-    lazy.flush()
-    limits = _color_limits(frames)
-    if phonon_history_out is not None:
-        f, ef, bins, meta = build_fixed_phonon_history(mask=mask, times=times, bath_temperature=bath_temperature,
-                                                       phonon_energy_bins=None)
-        phonon_history_out.update({"phonon_frames": f, "phonon_energy_frames": ef, "phonon_energy_bins": bins,
-                                   "phonon_metadata": meta})
-    return times, frames, mass, limits, None, None
+def _run_scalar(eng: Engine, sched, out: Outputs, inits, coefficients, enable_diffusion, bath_temperatures, histories,
+                scheme, rtol) -> list:
+    """Legacy scalar mode, energy_gap == 0 (solver.py:1517-1587), for M members as one [M, ncell] field set; the result
+    tuple of every member."""
+    mask, M = out.mask, out.members
+    u_host = np.stack([f[mask].astype(float) for f in inits])
+    u = eng.upload_packed(u_host)
+    diffuser = (_Diffuser(eng, M, sched.dt, sched.rem, scheme, rtol, dcoef=[float(D) for D in coefficients])
+                if enable_diffusion else None)
+    out.add_host_frames(0.0, [reconstruct_field(mask, v) for v in u_host],
+                        [float(np.sum(v) * out.dx * out.dx) for v in u_host])
+    scalar_loop(sched, diffuser, u, out, eng)
+    for T_bath, history in zip(bath_temperatures, histories):
+        if history is not None:
+            f, ef, bins, meta = build_fixed_phonon_history(mask=mask, times=out.times, bath_temperature=T_bath,
+                                                           phonon_energy_bins=None)
+            history.update({"phonon_frames": f, "phonon_energy_frames": ef, "phonon_energy_bins": bins,
+                            "phonon_metadata": meta})
+    return [(list(out.times), out.frames[m], out.mass[m], _color_limits(out.frames[m]), None, None) for m in range(M)]
 
 
 # ------------------------------------------------------------------------------------------------------------ #
