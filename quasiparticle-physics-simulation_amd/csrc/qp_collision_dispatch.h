@@ -40,7 +40,7 @@ struct WaveCollView {
 // n(t+dt) for dn/dt = gain - loss n with frozen coefficients (solver.py:640-665); wave and generic kernels
 __device__ __forceinline__ double relax_update(double n, double gain, double loss, double dt) {
   const double mu = fmax(loss, 0.0);
-  const double P = fmax(gain + (mu - loss) * n, 0.0);
+  const double P = fmax(gain + fmax(-loss, 0.0) * n, 0.0);      // mu - loss, safe from contraction (relax_update_f)
   const double decay = exp(-mu * dt);
   const double coeff = (mu < 1e-14) ? dt : (1.0 - decay) / mu;
   return fmax(decay * n + coeff * P, 0.0);

@@ -201,7 +201,10 @@ __device__ __forceinline__ void exp_small(double x, cdtab_t c, double& e, double
 template <bool FAST = true>
 __device__ __forceinline__ double relax_update_f(double n, double gain, double loss, double dt, cdtab_t ec) {
   const double mu = fmax(loss, 0.0);
-  const double P = fmax(fma(mu - loss, n, gain), 0.0);
+  // mu - loss of the reference, written as max(-loss, 0): the callers pass loss = dE * la, and with the subtraction spelled
+  // out the compiler contracts it to fma(-dE, la, mu) - not 0 but the rounding error of the product (half an ulp of the
+  // loss), which times n reached P: an absolute error of 1e-16 n in n', 1e-11 of n' in a bin that a long step depletes.
+  const double P = fmax(fma(fmax(-loss, 0.0), n, gain), 0.0);
   const double x = -mu * dt;
   // dt == 0 (wave-uniform; the reference returns the state unchanged): x = 0 with a finite rate, exp_small's g is NaN
   const bool small = FAST && fabs(x) < kPhiSmall, slow_rate = mu < 1e-14 || dt == 0.0;

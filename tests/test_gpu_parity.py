@@ -480,8 +480,10 @@ def test_collision_update_over_the_range_of_rate_times_step(O, ne, fmax, dt):
     """The exponential updates (solver.py:640-665, :686-700) over the regimes of x = rate * dt: dt = 0 (state returned
     unchanged - x = 0 with finite rates, where the small-|x| path of the NE < 30 kernels has no reciprocal), |x| ~ 1e-8
     (the reference's e^x - 1 is rounding-dominated there: the kernels reproduce that rounding instead of the closed form),
-    the small-|x| polynomial path proper, and |x| >> 1/8 (general path, clip to +-80; waves mix both paths pixel by pixel
-    through the occupation levels).  Against the oracle at the tolerances of the other collision tests."""
+    the small-|x| polynomial path proper, and |x| >> 1/8 (general path; waves mix both paths pixel by pixel through the
+    occupation levels).  The clip of the exponent to +-80 is barely reached: at dt = 25 b dt spans -18.4 ... 6.7 at NE = 12
+    (no clip) and -354 ... 69.3 at NE = 50 (the lower clip only); tests/test_gpu_collision_elementwise.py reaches both
+    clips with dt = 400 and 800.  Against the oracle at the tolerances of the other collision tests."""
     from qpsim_amd import tables as T
     from qpsim_amd.engine import CompiledGeometry, Engine, link_flags
     rng = np.random.default_rng(ne + 101)
