@@ -163,8 +163,14 @@ typedef struct qp_collision_tables {
  * qp_collision_member_tables_available(ne) is 1, (ncell / nclass) % 64 == 0, diag_bin / anti_bin are given and no FORCE bit
  * is set, the single-pass register kernel runs with every wave reading its own class's tables (bit-equal to one call per
  * class with that class's single table), and the double half-step call accepts the tables unless QP_COLL_SHARED_BINS is
- * set.  Everything else runs the one-wave-per-pixel or the generic kernel through cls, and the double half-step call returns
- * QP_ERR_UNSUPPORTED.  gap_sq / kr_amp / ks_amp / pair_inv / ks0_diag / kr0_anti2 are not used with this flag. */
+ * set.  Where qp_collision_onepass_available(ne) is 1 (ne = 30, 32, 40, 50), (ncell / nclass) % 256 == 0 - the 256-cell
+ * rule: a block of the one-pass kernel stages the tables of ONE class, so no block may straddle two - diag_bin / anti_bin are
+ * given and no FORCE bit is set, the one-pass kernel runs with every block reading its own class's tables (bit-equal to one
+ * call per class again).  It reads ks0_diag / kr0_anti2 with this flag, as [nclass][ne][ne] and [nclass][2ne-1][ne]: one
+ * image per class, each built from that class's ks0 / kr0 exactly as for one class; the image of an enabled process is
+ * required (there is no member form of the three-launch split kernels).  Everything else runs the one-wave-per-pixel or the
+ * generic kernel through cls, and the double half-step call returns QP_ERR_UNSUPPORTED.  gap_sq / kr_amp / ks_amp /
+ * pair_inv are not used with this flag. */
 #define QP_COLL_MEMBER_CLASSES 8u
 
 /*
@@ -234,7 +240,7 @@ int qp_collision_member_tables_available(int32_t ne);
  * pointers are tested for NULL, never followed).  Returns a QP_ROUTE_* value, or the negative status with which
  * qp_collision_step refuses the same tables.  QPSIM_COLL_ONEPASS=0 in the environment switches the one-pass routes off. */
 typedef enum qp_collision_route_kind {
-  QP_ROUTE_ONEPASS = 0,          /* one-pass kernel, one gap class (ks0_diag / kr0_anti2) */
+  QP_ROUTE_ONEPASS = 0,          /* one-pass kernel: one gap class, or one table per member class (ks0_diag / kr0_anti2) */
   QP_ROUTE_REGISTER = 1,         /* register kernel, one gap class (ne >= 32: three launches) */
   QP_ROUTE_REGISTER_MEMBERS = 2, /* register kernel with one table per member class */
   QP_ROUTE_ONEPASS_CLASSES = 3,  /* one-pass kernel, gap classes */

@@ -156,6 +156,11 @@ Route collision_route(const qp_collision_tables& t, long ncell, bool en_r, bool 
   // every other member-class table runs the one-wave-per-pixel or generic kernel below through `cls`
   if (reg && member_classes && collision_member_tables_supported(t.ne) && (ncell / t.nclass) % 64 == 0 && (s || r))
     return QP_ROUTE_REGISTER_MEMBERS;
+  // ... and at ne = 30, 32, 40, 50 the one-pass kernel, whose 256-pixel blocks stage the tables of their member: no block
+  // may straddle two members, and the diagonal-major tables are one per member as well.  No member form of the split kernels
+  if (reg && member_classes && collision_onepass_supported(t.ne) && (s || r) && (!s || t.ks0_diag) && (!r || t.kr0_anti2) &&
+      onepass_enabled() && (ncell / t.nclass) % 256 == 0)
+    return QP_ROUTE_ONEPASS;
   // gap classes with the separable kernel tables: the one-pass kernel where it exists ...
   if (reg && gap_classes && t.cls && t.gap_sq && t.pair_inv) {
     if (collision_onepass_classes_supported(t.ne) && t.nclass <= kOnePassMaxClasses && (s || r) && (!s || t.ks_amp) &&

@@ -15,7 +15,8 @@ QP_DEFINE_LOOKUP(onepassc_u0, QP_ONEPASS_CLASSES_NE_LIST(QP_LOOKUP_CASE, onepass
 QP_DEFINE_LOOKUP(onepassc_u1, QP_ONEPASS_CLASSES_NE_LIST(QP_LOOKUP_CASE, onepassc_u1))
 
 // The two one-pass routes of collision_route.  Gap classes: the separable kernel tables (gap_sq, kr_amp, ks_amp, pair_inv)
-// instead of kr0 / ks0 and their diagonal-major copies - the same kernel with K formed per lane.
+// instead of kr0 / ks0 and their diagonal-major copies - the same kernel with K formed per lane.  Member tables
+// (QP_COLL_MEMBER_CLASSES) are QP_ROUTE_ONEPASS with the member extent filled in: each block stages its member's set.
 void collision_onepass_dispatch(Route route, const qp_collision_tables& t, const CollCall& c) {
   OnePassView v{};
   onepass_launcher_t fn = nullptr;
@@ -24,6 +25,10 @@ void collision_onepass_dispatch(Route route, const qp_collision_tables& t, const
                           nullptr, 0.0};
     v.ksd = t.ks0_diag;
     v.kra2 = t.kr0_anti2;
+    if ((t.flags & QP_COLL_MEMBER_CLASSES) && t.nclass > 1) {
+      assert((c.ncell / t.nclass) % kOnePassThreads == 0 && "collision_route let a block straddle two members");
+      v.member_blocks = (unsigned)(c.ncell / t.nclass / kOnePassThreads);
+    }
     fn = find_onepass(t.ne, c.s, c.r);
   } else {
     v.base = CollFastView{nullptr, nullptr, t.rho, t.diag_bin, t.anti_bin, c.stash, t.cls, t.gap_sq,

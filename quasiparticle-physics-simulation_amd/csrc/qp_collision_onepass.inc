@@ -52,6 +52,8 @@ struct OnePassView {
   const double* ksd;       // [NE][NE]     ksd[k NE + i]  = ks0[i][i - k]      (phase 2)
   const double* kra2;      // [2NE-1][NE]  kra2[m NE + i] = 2 kr0[i][m - i]    (phase 2)
   int nclass;              // gap-class form (PARAM kernels): base.cls, gap_sq, kr_amp, ks_amp, pair_inv, rho[nclass][NE]
+  unsigned member_blocks;  // member tables (the other kernels): blocks per ensemble member - block b stages table set
+                           // b / member_blocks of kr0, ks0, rho, ksd, kra2; 0: one shared set
 };
 
 constexpr int kOnePassThreads = 256;
@@ -108,17 +110,21 @@ collision_onepass_kernel(OnePassView w, const uint8_t* __restrict__ flags, long 
   const unsigned p = (unsigned)(in_grid ? pg : ncell - 1);       // lanes past the end compute on the last cell, store nothing
   const bool live = in_grid && (flags[p] & QP_FLAG_ACTIVE);
   const cdtab_t ec = exp_table();
+  // Member tables: all cells of a block belong to one ensemble member (the route sees to it), so the block stages that
+  // member's tables and everything behind the staging loops is the kernel of a lone call - bit-equal results.  Scalar code.
+  const long mb = (!PARAM && w.member_blocks) ? (long)(blockIdx.x / w.member_blocks) : 0L;
 
   // ---- stage the phase-1 tables ------------------------------------------------------------------------------------------
   {
     const int tid = threadIdx.x;
-    if (USE_S) for (int e = tid; e < NE * NE; e += kOnePassThreads) lds[L::kKs + e] = PARAM ? t.ks_amp[e] : t.ks0[e];
-    if (USE_R) for (int e = tid; e < NE * NE; e += kOnePassThreads) lds[L::kKr + e] = PARAM ? t.kr_amp[e] : t.kr0[e];
+    const long mt = mb * (NE * NE);
+    if (USE_S) for (int e = tid; e < NE * NE; e += kOnePassThreads) lds[L::kKs + e] = PARAM ? t.ks_amp[e] : t.ks0[mt + e];
+    if (USE_R) for (int e = tid; e < NE * NE; e += kOnePassThreads) lds[L::kKr + e] = PARAM ? t.kr_amp[e] : t.kr0[mt + e];
     if (PARAM) {
       for (int e = tid; e < NE * NE; e += kOnePassThreads) lds[L::kPi + e] = t.pair_inv[e];
       for (int e = tid; e < w.nclass * NE; e += kOnePassThreads) lds[L::kRho + e] = t.rho[e];
     } else if (tid < NE) {
-      lds[L::kRho + tid] = t.rho[tid];
+      lds[L::kRho + tid] = t.rho[mb * NE + tid];
     }
     // byte offsets of the phonon planes as 64-bit integers in the same array
     if (USE_S && tid < NE) reinterpret_cast<long*>(lds)[L::kOffD + tid] = (long)bin_of(t.diag_bin[tid]) * ncell * 8;
@@ -368,8 +374,9 @@ collision_onepass_kernel(OnePassView w, const uint8_t* __restrict__ flags, long 
             }
           }
       } else {
-        if (USE_S) for (int e = tid; e < NE * NE; e += kOnePassThreads) lds[L::kKsd + e] = w.ksd[e];
-        if (USE_R) for (int e = tid; e < (2 * NE - 1) * NE; e += kOnePassThreads) lds[L::kKra + e] = w.kra2[e];
+        if (USE_S) for (int e = tid; e < NE * NE; e += kOnePassThreads) lds[L::kKsd + e] = w.ksd[mb * (NE * NE) + e];
+        if (USE_R)
+          for (int e = tid; e < (2 * NE - 1) * NE; e += kOnePassThreads) lds[L::kKra + e] = w.kra2[mb * ((2 * NE - 1) * NE) + e];
       }
       if (USE_S && tid < NE) reinterpret_cast<long*>(lds)[L::kOffD2 + tid] = (long)bin_of(t.diag_bin[tid]) * ncell * 8;
       if (USE_R && tid < 2 * NE - 1) reinterpret_cast<long*>(lds)[L::kOffA2 + tid] = (long)bin_of(t.anti_bin[tid]) * ncell * 8;

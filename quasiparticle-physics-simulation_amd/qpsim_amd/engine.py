@@ -222,6 +222,15 @@ def antidiagonal_major(table: np.ndarray, scale: float = 1.0) -> np.ndarray:
     return out
 
 
+def onepass_tables(ks0, kr0, nclass: int, ne: int):
+    """(ks0_diag, kr0_anti2) of the one-pass collision kernel (qpsim_hip.h): ``diagonal_major(ks0)`` [nclass, ne, ne] and
+    ``antidiagonal_major(kr0, 2.0)`` [nclass, 2 ne - 1, ne], one image per table - the image of class m is that of its table
+    alone, so a member's slice is what a lone call uploads.  None for a table that is None."""
+    ksd = None if ks0 is None else diagonal_major(np.asarray(ks0, dtype=np.float64).reshape(nclass, ne, ne))
+    kra = None if kr0 is None else antidiagonal_major(np.asarray(kr0, dtype=np.float64).reshape(nclass, ne, ne), 2.0)
+    return ksd, kra
+
+
 def tag_merged_bins(diag, anti):
     """(diag, anti, n_merged): entries of a phonon bin fed by both a diagonal k >= 1 and an anti-diagonal m get
     (slot + 1) << 16 added, slot numbering the merged bins (what the register collision kernels expect, qpsim_hip.h)."""
@@ -843,7 +852,9 @@ class Engine:
         ``members`` > 1: the class map is repeated over an ensemble laid out [member][cell] (same tables for every member).
         ``member_classes``: the C tables are one set per ensemble member instead (``QP_COLL_MEMBER_CLASSES``: ``members``
         = C, class m = the cells of member m).  The register kernels read them for NE = 4 ... 16 when a member's cell count
-        is a multiple of 64; other shapes and larger NE run the one-wave-per-pixel kernel through the class map."""
+        is a multiple of 64, the one-pass kernel for NE = 30, 32, 40, 50 when it is a multiple of 256 (the handle then
+        carries ``ks0_diag`` / ``kr0_anti2`` per member and reports ``kernel == "register"``); other shapes and sizes run
+        the one-wave-per-pixel kernel through the class map."""
         torch = self.torch
         up = lambda a, dt: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.device)  # noqa: E731
         rho = np.atleast_2d(np.asarray(rho, dtype=np.float64))
@@ -914,19 +925,23 @@ class Engine:
         # member classes: the register kernels' member-table form where it exists, decided per call by the member's cell
         # count (the merged-bin stash is sized for it either way)
         members_ok = bool(member_classes and self.lib.qp_collision_member_tables_available(ne))
+        # ... and at the one-pass sizes that kernel, whose 256-pixel blocks each stage the tables of one member
+        members_onepass = bool(member_classes and kernel == "auto" and structure is not None and symmetric
+                               and self.ncell % 256 == 0 and self.lib.qp_collision_onepass_available(ne))
         h["member_classes"] = bool(member_classes)
         h["kernel"] = ("generic" if (kernel == "generic" or not wave_ok) else
                        "register" if (kernel == "auto" and structure is not None
-                                      and (members_ok if member_classes else (nclass == 1 or classes_ok))
+                                      and ((members_ok or members_onepass) if member_classes else (nclass == 1 or classes_ok))
                                       and bool(self.lib.qp_collision_register_kernel_available(ne))) else "wave")
         h["fast"] = h["kernel"] != "generic"      # no accumulator planes needed
         # one-pass kernel (ne = 30, 32, 40, 50): the kernel tables once more in (anti)diagonal-major order (qpsim_hip.h)
         h["ks0_diag"] = h["kr0_anti2"] = None
-        if (h["kernel"] == "register" and nclass == 1 and symmetric and bool(self.lib.qp_collision_onepass_available(ne))):
-            if ks0 is not None:
-                h["ks0_diag"] = up(diagonal_major(np.asarray(ks0).reshape(ne, ne)), np.float64)
-            if kr0 is not None:
-                h["kr0_anti2"] = up(antidiagonal_major(np.asarray(kr0).reshape(ne, ne), 2.0), np.float64)
+        # (member classes: one image per member)
+        if (h["kernel"] == "register" and (nclass == 1 or members_onepass) and symmetric
+                and bool(self.lib.qp_collision_onepass_available(ne))):
+            ksd, kra = onepass_tables(ks0, kr0, nclass, ne)
+            h["ks0_diag"] = up(ksd if nclass > 1 or ksd is None else ksd[0], np.float64)
+            h["kr0_anti2"] = up(kra if nclass > 1 or kra is None else kra[0], np.float64)
         # consecutive half-steps of neighbouring Strang steps in one pass (qp_collision_double_step_guarded)
         h["pair"] = bool(h["kernel"] == "register" and (nclass == 1 or members_ok) and structure is not None and not shared
                          and symmetric

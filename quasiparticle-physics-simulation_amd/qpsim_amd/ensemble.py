@@ -10,8 +10,10 @@ Parameter sweeps: ``sweep={"tau_0": [...], "T_c": [...], ...}`` (keys of ``SWEEP
 collision physics over the members.  Every member then has its own K^r_0 / K^s_0 / rho tables on the device (built on the
 host exactly as its lone run builds them); with NE = 4 ... 16 and a member cell count that is a multiple of 64 the register
 collision kernels - single pass and double half-step - read the table of the wave's member, bit-equal to the lone tables;
-other shapes and larger NE run the one-wave-per-pixel kernel through a member class map and two calls instead of the pair
-pass.  A sweep whose members all end up with the same tables runs exactly as the call without ``sweep``.
+with NE = 30, 32, 40, 50 (the default 50 included) and a member cell count that is a multiple of 256 every block of the
+one-pass collision kernel stages the tables of its member, bit-equal as well; other shapes and sizes run the
+one-wave-per-pixel kernel through a member class map.  Outside NE = 4 ... 16 a step pair takes two calls instead of the
+pair pass.  A sweep whose members all end up with the same tables runs exactly as the call without ``sweep``.
 
 Rounding: members are bit-equal to their lone ``run_2d_crank_nicolson`` call with ``diffusion_scheme="adi"`` when both use
 the same ADI tile family (``QPSIM_FINE_TILES``) and the same step form (``QPSIM_ADI_FUSED``: a batch of at least 4 Mi
@@ -145,7 +147,8 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
     default from that member's ``tau_0``; its ``dynes_gamma`` also shapes its initial state and its Pauli guard).  A swept
     key must not be set to another value in ``common``, and a sweep cannot be combined with ``precomputed`` or
     ``gap_expression``.  The register collision kernels serve per-member tables for ``num_energy_bins`` 4 ... 16 when the
-    member's device grid holds a multiple of 64 cells; larger NE and other grids run the one-wave-per-pixel kernel.
+    member's device grid holds a multiple of 64 cells, the one-pass kernel for 30, 32, 40 and 50 (the default) when it holds
+    a multiple of 256; other sizes and grids run the one-wave-per-pixel kernel.
     Entry m is the 6-tuple member m's lone call returns (its ``phonon_history_out`` filled the same
     way), or - with ``errors="return"`` - the ``ValueError`` its Pauli guard raised (the other members finish).  With
     ``errors="raise"`` the first violation (earliest step, then lowest member) raises ``ValueError("member m: ...")``.

@@ -5,10 +5,15 @@
   (b) 512 members x 64^2 at NE = 50 next to 512 sequential lone `run_2d_crank_nicolson` calls;
   (c) a parameter sweep at the c4 shape: the same ensemble without a sweep, with `sweep={"tau_0": 64 distinct values}` (the
       register kernels read per-member tables) and that sweep forced onto the class-map kernels (QPSIM_MEMBER_TABLES=0).
+  (d) `sweep50`, a parameter sweep at the reference's default resolution: 512 members x 64^2, NE = 50, the same three
+      variants with 512 distinct tau_0 (member tables: the one-pass kernel stages each block's member; QPSIM_MEMBER_TABLES=0:
+      the one-wave-per-pixel kernel through the class map), then the collision step alone (device events) with the three
+      table forms.
 Each figure is the difference of two run lengths (setup, first / last store excluded).
 Case (c) also times the double half-step pass alone (device events) with one shared and with per-member tables.
-python tools/exp_ensemble.py [--case all|api|sweep] [--repeat N] [--steps K]"""
+python tools/exp_ensemble.py [--case all|api|sweep|sweep50] [--repeat N] [--steps K] [--json FILE]"""
 import argparse
+import json
 import os
 import sys
 import time
@@ -90,14 +95,60 @@ def pair_pass_alone(repeat=1, calls=20):
                       f"{ev[0].elapsed_time(ev[1]) / calls:.4f} ms per pass", flush=True)
 
 
-def sweep_case(repeat=1, steps=100):
-    """(c): ms/step and pair passes of the c4-shape ensemble without a sweep, with 64 distinct tau_0, and with that sweep on
-    the class-map kernels; `repeat` rounds, the three variants alternating within a round."""
-    N, M = 256, 64
+def collision_step_alone(repeat=1, calls=10, N=64, M=512, ne=50):
+    """Device time of one collision step over M x N^2 pixels (both processes, dynamic phonons): one shared table set, M
+    member table sets, and the member sets through the class map (QPSIM_MEMBER_TABLES=0), alternating.  Returns
+    {variant: [ms per call ...]}."""
+    from qpsim_amd import tables as T
+    from qpsim_amd.engine import CompiledGeometry, Engine, link_flags
+    mask = np.ones((N, N), dtype=bool)
+    z = np.zeros(mask.shape)
+    eng = Engine(CompiledGeometry(mask, 1.0, link_flags(mask), z, z, z, z))
+    ncm = eng.ncell
+    E, dE = T.build_energy_grid(180.0, 1.0, 3.0, ne)
+    om, idx_d, idx_s, sg = T.build_phonon_frequency_map(E)
+    rho = T.dynes_density_of_states(E, 180.0, 0.0)
+    tau = [300.0 + 320.0 * m / M for m in range(M)]
+    kr = np.stack([T.recombination_kernel_base(E, 180.0, t, 1.2) for t in tau])
+    ks = np.stack([T.scattering_kernel_base(E, 180.0, t, 1.2) for t in tau])
+    member = lambda: eng.make_collision_tables(kr, ks, np.tile(rho, (M, 1)), idx_d, idx_s, sg, None, members=M,  # noqa: E731
+                                               member_classes=True)
+    tabs = {"shared tables": eng.make_collision_tables(kr[:1], ks[:1], rho[None], idx_d, idx_s, sg), "member tables": member()}
+    os.environ["QPSIM_MEMBER_TABLES"] = "0"
+    try:
+        tabs["member tables, class-map kernel"] = member()
+    finally:
+        os.environ.pop("QPSIM_MEMBER_TABLES", None)
+    rng = np.random.default_rng(0)
+    w = rho / (rho.sum() * dE)
+    s0 = torch.as_tensor(w[:, None] * (1e-4 * (1.0 + rng.random(M * ncm)))[None, :], device=eng.device)
+    ph0 = torch.as_tensor(np.repeat(T.thermal_phonon_occupation(om, 0.1)[:, None], M * ncm, axis=1), device=eng.device)
+    out, ph = torch.empty_like(s0), ph0.clone()
+    flags = eng.d_flags.reshape(-1).repeat(M)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    found = {name: [] for name in tabs}
+    for r in range(repeat + 1):                                  # round 0 warms up
+        for name, tab in tabs.items():
+            ph.copy_(ph0)
+            ev[0].record()
+            for _ in range(calls):
+                eng.collide(tab, s0, out, ph, dE, 0.05, True, True, True, ncell=M * ncm, flags=flags)
+            ev[1].record()
+            torch.cuda.synchronize()
+            if r:
+                found[name].append(round(ev[0].elapsed_time(ev[1]) / calls, 4))
+                print(f"collision step alone, {M} x {N}^2 NE={ne}, round {r - 1}: {name} ({tab['kernel']}): "
+                      f"{found[name][-1]:.4f} ms per call", flush=True)
+    return found
+
+
+def sweep_case(repeat=1, steps=100, N=256, M=64, ne=12, label="c4 shape", short=5):
+    """(c) / (d): ms/step and pair passes of an ensemble without a sweep, with M distinct tau_0, and with that sweep on the
+    class-map kernels; `repeat` rounds, the three variants alternating within a round.  Returns {variant: [ms/step ...]}."""
     rng = np.random.default_rng(0)
     members = [{"initial_field": 1e-4 * (1.0 + rng.random((N, N)))} for _ in range(M)]
-    kw = common(N, 12)
-    tau = [300.0 + 5.0 * m for m in range(M)]
+    kw = common(N, ne)
+    tau = [300.0 + 320.0 * m / M for m in range(M)]
     variants = [("no sweep", None, "1"), ("sweep tau_0, member tables", {"tau_0": tau}, "1"),
                 ("sweep tau_0, class-map kernels", {"tau_0": tau}, "0")]
 
@@ -112,19 +163,35 @@ def sweep_case(repeat=1, steps=100):
 
     for _, sweep, knob in variants:
         runner(sweep, knob)(3)
+    found = {name: [] for name, _, _ in variants}
     for r in range(repeat):
         for name, sweep, knob in variants:
-            ms = per_step(runner(sweep, knob), 5, 5 + steps)
-            print(f"c4 shape {M} x {N}^2 NE=12, round {r}: {name}: {ms:.3f} ms/step, pair passes in the {5 + steps}-step run: "
-                  f"{last_run_stats()['pair_passes']}", flush=True)
+            ms = per_step(runner(sweep, knob), short, short + steps)
+            found[name].append(round(ms, 4))
+            print(f"{label} {M} x {N}^2 NE={ne}, round {r}: {name}: {ms:.3f} ms/step, pair passes in the {short + steps}-step "
+                  f"run: {last_run_stats()['pair_passes']}", flush=True)
+    return found
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=["all", "api", "sweep"], default="all")
+    ap.add_argument("--case", choices=["all", "api", "sweep", "sweep50"], default="all")
     ap.add_argument("--repeat", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100, help="step difference of the two run lengths of case (c)")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="step difference of the two run lengths of case (c) (default 100) and (d) (default 30)")
+    ap.add_argument("--json", default=None, help="case sweep50: also write the ms/step figures to this file")
     args = ap.parse_args()
+    if args.case == "sweep50":
+        steps = args.steps or 30
+        found = sweep_case(args.repeat, steps, N=64, M=512, ne=50, label="sweep50", short=2)
+        alone = collision_step_alone(args.repeat)
+        if args.json:
+            Path(args.json).write_text(json.dumps(
+                {"case": "sweep50", "members": 512, "grid": [64, 64], "num_energy_bins": 50, "steps": steps,
+                 "device": torch.cuda.get_device_name(), "ms_per_step": found, "collision_step_alone_ms": alone},
+                indent=1) + "\n")
+        return
+    args.steps = args.steps or 100
     if args.case in ("all", "api"):
         api_cases()
     if args.case in ("all", "sweep"):
