@@ -274,6 +274,63 @@ int qp_nan_pad(const uint8_t* flags, int64_t ncell, int32_t nfield, const double
 int qp_add_scaled(int64_t n, double* state, const double* g, double scale, void* stream);
 
 /*
+ * Custom generation g(E, x, y, t, params) evaluated on the device (replaces the host evaluation + upload of
+ * solver.py:918-962 and the update of solver.py:1464 for expressions in the device subset).
+ *
+ * The host splits the expression: every sub-expression that names neither x nor y is evaluated on the host per step and
+ * energy bin and arrives as slots[bin][slot]; what mixes x, y with slots arrives as a register program of `nword`
+ * instruction words, each
+ *     op | dst << 8 | a << 12 | b << 18 | c << 24          (op 8 bits, dst 4 bits, operands 6 bits)
+ * with dst a register 0 .. QP_EXPR_MAX_REGS-1 and an operand one of: 0 .. 7 a register, QP_EXPR_X, QP_EXPR_Y, or
+ * QP_EXPR_SLOT0 + k for slot k < nslot.  The value of the program is what its LAST word writes.  Registers are read only
+ * after they were written (checked).  Arithmetic is IEEE fp64 without contraction: +, -, *, /, sqrt are correctly rounded,
+ * MAX / MIN propagate NaN as np.maximum / np.minimum do, a comparison yields 0.0 or 1.0, WHERE takes a when c != 0,
+ * HEAVISIDE(a, b) is np.heaviside; POW and the transcendental ops are the device math library's (not bit-equal to NumPy).
+ * Coordinates are the pixel centres of the FULL mask, x = (col0 + col + 0.5) / nx_full, y = (row0 + row + 0.5) / ny_full
+ * (one IEEE division each, solver.py:924-929); the ny x nx device grid is the window at (row0, col0) of that mask.
+ */
+enum {
+  QP_EXPR_MAX_WORDS = 64, /* instruction words of a program */
+  QP_EXPR_MAX_REGS = 8,   /* live temporaries */
+  QP_EXPR_MAX_SLOTS = 16, /* host-evaluated values per energy bin */
+  QP_EXPR_X = 8,
+  QP_EXPR_Y = 9,
+  QP_EXPR_SLOT0 = 16
+};
+typedef enum qp_expr_op {
+  QP_OP_COPY = 0, QP_OP_NEG, QP_OP_ADD, QP_OP_SUB, QP_OP_MUL, QP_OP_DIV, QP_OP_POW, QP_OP_SQUARE, QP_OP_SQRT, QP_OP_RECIP,
+  QP_OP_ABS, QP_OP_MAX, QP_OP_MIN, QP_OP_WHERE /* c ? a : b */, QP_OP_HEAVISIDE, QP_OP_LT, QP_OP_LE, QP_OP_GT, QP_OP_GE,
+  QP_OP_EQ, QP_OP_NE, QP_OP_EXP, QP_OP_LOG, QP_OP_LOG10, QP_OP_SIN, QP_OP_COS, QP_OP_TAN, QP_OP_ASIN, QP_OP_ACOS,
+  QP_OP_ATAN, QP_OP_SINH, QP_OP_COSH, QP_OP_TANH, QP_OP_COUNT
+} qp_expr_op;
+typedef struct qp_generation_program {
+  uint32_t struct_size;    /* sizeof(qp_generation_program) as the CALLER compiled it */
+  int32_t ny, nx;          /* device grid of one member; ncell_member = ny*nx */
+  int32_t ny_full, nx_full; /* extent of the full mask that defines x, y */
+  int32_t row0, col0;      /* position of the device grid inside the full mask */
+  int32_t ne;              /* energy bins */
+  int32_t nslot;           /* slots per bin, 0 .. QP_EXPR_MAX_SLOTS */
+  int32_t nword;           /* 1 .. QP_EXPR_MAX_WORDS */
+  const uint32_t* words;   /* [nword] HOST memory: validated by the call and passed to the kernel by value */
+  const double* slots;     /* [ne][nslot] device memory (host memory for qp_expr_eval_host); NULL when nslot == 0 */
+} qp_generation_program;
+/*
+ * state[bin][m][c] += dt * g(bin, c) for every interior cell c of the listed members m over planes laid out
+ * [bin][member][cell] (`members` members of ny*nx cells; flags cover members * ncell_member cells as in
+ * qp_add_constant_members).  member_ids: device array of `nlisted` member indices, or NULL for all members
+ * (nlisted == members).  The update rounds as qp_add_scaled does on the g the program evaluates to.  Cells outside the mask
+ * are neither evaluated nor written.  status: two device words, zeroed by the call on `stream` before the kernel runs;
+ * the kernel ORs 1 into status[0] when a value it added was not finite and into status[1] when one was negative
+ * (the checks of solver.py:895-902, left to the caller to read back).
+ */
+int qp_add_generation_expr(const qp_generation_program* prog, const uint8_t* flags, int64_t members,
+                           const int32_t* member_ids, int64_t nlisted, double* state, double dt, uint32_t* status,
+                           void* stream);
+/* Test hook: the same evaluator function compiled for the host.  out[bin][row * nx + col] = g for EVERY cell of the
+ * ny x nx grid (all pointers host memory, no flags, no update).  The product never calls it. */
+int qp_expr_eval_host(const qp_generation_program* prog, double* out);
+
+/*
  * Pauli-guard statistics over state[ne][ncell] (solver.py:967-996): occupation f = n / rho where rho > 1e-30.
  * out_vals[0] = max f, out_idx[0] = its linear index ie*ncell + p (first in C order on ties; a NaN occupation counts as
  * the maximum and the first NaN wins, as np.argmax does),

@@ -42,6 +42,13 @@ class CollisionTables(_SizedStructure):
                 ("ks0_diag", c_dp), ("kr0_anti2", c_dp)]
 
 
+class GenerationProgram(_SizedStructure):
+    """Mirror of ``qp_generation_program`` (``words`` is host memory; ``slots`` device memory, host for the test hook)."""
+    _fields_ = [("struct_size", C.c_uint32), ("ny", C.c_int32), ("nx", C.c_int32), ("ny_full", C.c_int32),
+                ("nx_full", C.c_int32), ("row0", C.c_int32), ("col0", C.c_int32), ("ne", C.c_int32), ("nslot", C.c_int32),
+                ("nword", C.c_int32), ("words", c_dp), ("slots", c_dp)]
+
+
 # qp_collision_route_kind: what qp_collision_route returns for tables it accepts
 (ROUTE_ONEPASS, ROUTE_REGISTER, ROUTE_REGISTER_MEMBERS, ROUTE_ONEPASS_CLASSES, ROUTE_REGISTER_CLASSES, ROUTE_WAVE,
  ROUTE_GENERIC, ROUTE_COPY) = range(8)
@@ -77,6 +84,9 @@ SIGNATURES = {
                                      C.c_int, c_dp]),
     "qp_add_constant": (C.c_int, [c_dp, C.c_int64, C.c_int32, c_dp, C.c_double, c_dp]),
     "qp_add_scaled": (C.c_int, [C.c_int64, c_dp, c_dp, C.c_double, c_dp]),
+    "qp_add_generation_expr": (C.c_int, [C.POINTER(GenerationProgram), c_dp, C.c_int64, c_dp, C.c_int64, c_dp, C.c_double,
+                                         c_dp, c_dp]),
+    "qp_expr_eval_host": (C.c_int, [C.POINTER(GenerationProgram), c_dp]),
     "qp_pauli_workspace_bytes": (C.c_int64, []),
     "qp_pauli_stats": (C.c_int, [c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_int64, C.c_double, c_dp, c_dp,
                                  c_dp, c_dp]),

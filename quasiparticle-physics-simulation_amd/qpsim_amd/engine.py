@@ -515,12 +515,14 @@ class Engine:
         self._scratch = {}
         self._pinned_stream = None
         # made at their first use: download staging rings, guard workspace, pinned guard read-back slots (lone: a ring;
-        # ensembles: result buffer + ring per ensemble size), device vectors of per-member generation amounts
+        # ensembles: result buffer + ring per ensemble size), device vectors of per-member generation amounts, staging / status
+        # ring of the device-evaluated custom generation
         self._dl_slots = None
         self._guard_ws = None
         self._guard_slots = None
         self._mguard: dict = {}
         self._amount_vectors: dict = {}
+        self._gen_slots = None
 
     # -- plumbing -------------------------------------------------------------------------------------------
     @property
@@ -1046,6 +1048,74 @@ class Engine:
 
     def add_scaled(self, state, g, scale: float):
         _hip.check(self.lib.qp_add_scaled(state.numel(), _ptr(state), _ptr(g), float(scale), self.stream), "qp_add_scaled")
+
+    def _generation_slot(self, nbytes: int, nlaunch: int):
+        """Next slot of the generation ring, GUARD_LAG + 1 beside the guard's: a pinned staging buffer with its device
+        image for the slot tables and member lists of a step, the two status words per launch on the device with their
+        pinned read-back image, and the event recorded behind that read-back.  A time loop reads the status of step k
+        before it enqueues step k + GUARD_LAG + 1, so a slot is free when its turn comes again (its event is waited for
+        all the same)."""
+        torch = self.torch
+        if self._gen_slots is None:
+            self._gen_slots = [{"host": None, "dev": None, "status_host": None, "status_dev": None,
+                                "event": torch.cuda.Event(), "open": False} for _ in range(self.GUARD_LAG + 1)]
+            self._gen_next = 0
+        slot = self._gen_slots[self._gen_next]
+        self._gen_next = (self._gen_next + 1) % len(self._gen_slots)
+        if slot["open"]:
+            slot["event"].synchronize()
+        if slot["host"] is None or slot["host"].numel() < nbytes:
+            slot["host"] = torch.empty(max(nbytes, 1024), dtype=torch.uint8).pin_memory()
+            slot["dev"] = torch.empty(max(nbytes, 1024), dtype=torch.uint8, device=self.device)
+        if slot["status_host"] is None or slot["status_host"].numel() < 2 * nlaunch:
+            slot["status_host"] = torch.zeros(2 * nlaunch, dtype=torch.int32).pin_memory()
+            slot["status_dev"] = torch.zeros(2 * nlaunch, dtype=torch.int32, device=self.device)
+        return slot
+
+    def add_generation_expr(self, state, window, launches, dt: float, members: int, flags):
+        """state[bin][m][c] += dt * g on the interior cells of the listed members, g evaluated by ``qp_add_generation_expr``
+        (custom generation in the device subset, ``device_expr``).  ``launches``: ``(words, slot table [NE, nslot], member
+        list or None for all)`` per distinct program; ``window`` = (ny_full, nx_full, row0, col0) places the engine grid in
+        the full mask whose pixel centres are x, y.  The tables and lists go up in one asynchronous copy from pinned
+        memory; the status words of all launches come back in one, as the guard's do.  Returns a ticket for
+        ``generation_status``."""
+        members = int(members)
+        ne = state.numel() // (self.ncell * members)
+        offsets, nbytes = [], 0
+        for words, table, listed in launches:
+            ids = None if listed is None else np.asarray(listed, dtype=np.int32)
+            offsets.append((nbytes, ids, nbytes + table.nbytes))
+            nbytes += table.nbytes + (0 if ids is None else 8 * ((ids.nbytes + 7) // 8))
+        slot = self._generation_slot(nbytes, len(launches))
+        staging = slot["host"].numpy()
+        for (words, table, _), (at, ids, ids_at) in zip(launches, offsets):
+            staging[at:at + table.nbytes] = np.ascontiguousarray(table, dtype=np.float64).reshape(-1).view(np.uint8)
+            if ids is not None:
+                staging[ids_at:ids_at + ids.nbytes] = ids.view(np.uint8)
+        if nbytes:
+            slot["dev"][:nbytes].copy_(slot["host"][:nbytes], non_blocking=True)
+        base, status = _ptr(slot["dev"]), _ptr(slot["status_dev"])
+        ny_full, nx_full, row0, col0 = (int(v) for v in window)
+        for k, ((words, table, _), (at, ids, ids_at)) in enumerate(zip(launches, offsets)):
+            words = np.ascontiguousarray(words, dtype=np.uint32)
+            prog = _hip.GenerationProgram.make(self.ny, self.nx, ny_full, nx_full, row0, col0, ne, table.shape[1], words.size,
+                                               words.ctypes.data, base + at if table.shape[1] else 0)
+            _hip.check(self.lib.qp_add_generation_expr(C.byref(prog), _ptr(flags), members, 0 if ids is None else base + ids_at,
+                                                       members if ids is None else ids.size, _ptr(state), float(dt),
+                                                       status + 8 * k, self.stream), "qp_add_generation_expr")
+        n = 2 * len(launches)
+        slot["status_host"][:n].copy_(slot["status_dev"][:n], non_blocking=True)
+        slot["event"].record(self.torch.cuda.current_stream(self.device))
+        slot["open"] = True
+        return slot, len(launches)
+
+    def generation_status(self, ticket) -> list:
+        """[(a value was not finite, a value was negative)] per launch of an ``add_generation_expr`` ticket."""
+        slot, nlaunch = ticket
+        slot["event"].synchronize()
+        slot["open"] = False
+        words = slot["status_host"][:2 * nlaunch].numpy()
+        return [(bool(words[2 * k]), bool(words[2 * k + 1])) for k in range(nlaunch)]
 
     def pauli_stats(self, state, tables, floor: float):
         """(max occupation, (energy index, cell index), forbidden (energy, cell) or None)."""

@@ -27,6 +27,7 @@ import warnings
 
 import numpy as np
 
+from . import device_expr
 from . import solver as S
 from .distributed import shard_members
 from .engine import Engine
@@ -160,6 +161,7 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
     kws = member_arguments(list(members), common, sweep)
     _STATS.clear()
     _STATS.update(batches=0, pair_passes=0, guarded_calls=0)
+    device_expr.reset_run_stats()
     if not kws:
         return []
     world, rank = 1, 0
@@ -260,17 +262,39 @@ class _MembersRun(EnergyRun):
         self.members = self.out.members
         self.warned = [False] * self.members
         self.failed: list = [None] * self.members
+        self.step = 0              # generate() is called once per step: the step its status tickets belong to
+        self.status: list = []
+
+    def _generate_on_device(self, custom: list, t: float, dt_step: float) -> list:
+        """Launches the device evaluator for the members of ``custom`` whose expression it serves at this step - one launch
+        per distinct program, members with the same body, words and slots sharing it - and returns the members left to the
+        host path."""
+        gens, launches, host = self.generations, {}, []
+        for m in custom:
+            launch = gens[m].device_step(t)
+            if launch is None:
+                host.append(m)
+                continue
+            key = (gens[m].program.body, launch[0].tobytes(), launch[1].tobytes())
+            launches.setdefault(key, launch + ([],))[2].append(m)
+        if launches:
+            self.status.append((self.step, self.eng.add_generation_expr(
+                self.state, gens[custom[0]].window, list(launches.values()), dt_step, self.members, self.flags)))
+        device_expr.count_steps(device=len(custom) - len(host), host=len(host))
+        return host
 
     def generate(self, t: float, dt_step: float) -> None:
         gens, eng, M = self.generations, self.eng, self.members
+        self.step += 1
         if not any(g.active for g in gens):
             return
         amounts = generation_amounts([g.spec for g in gens], t, dt_step)
-        if any(x is None for x in amounts):                      # custom expressions: evaluated on the host
+        custom = self._generate_on_device([m for m, x in enumerate(amounts) if x is None], t, dt_step)
+        if custom:                                               # custom expressions evaluated on the host
             n = int(np.sum(self.out.mask))
             g = np.zeros((self.state.shape[0] // M, M, n))
-            for m, x in enumerate(amounts):
-                g_ext = gens[m].rates(t) if x is None else None
+            for m in custom:
+                g_ext = gens[m].rates(t)
                 if g_ext is not None:
                     g[:, m] = g_ext
             eng.add_scaled(self.state, eng.upload_packed(g.reshape(-1, n)), dt_step)
@@ -303,6 +327,7 @@ class _MembersRun(EnergyRun):
                                                    self.flags)
 
     def guard_check(self, ticket, step: int, t: float) -> None:
+        S._check_generation_status(self.eng, self.status, step)
         for m, stats in enumerate(self.eng.pauli_stats_members_result(ticket)):
             # no forbidden density and no occupation above the lower threshold: the member has nothing to report
             if self.failed[m] is not None or (stats[2] is None and not stats[0] > self.quiet_below):
@@ -356,7 +381,8 @@ def _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, taus):
     run = _MembersRun(eng, out, state, eng.empty(NE * M, ncm), eng.upload_packed(phonon_host), dE,
                       S._phonon_widths(eng, omega_bins, dE, histories))
     run.ctab, run.floor, run.physics = ctab, a["pauli_density_floor"], (en_r, en_s, not a["freeze_phonon_dynamics"])
-    run.flags, run.generations = flags, [S._Generation(k["external_generation"], mask, E_bins) for k in kws]
+    run.flags, run.generations = flags, [
+        S._Generation(k["external_generation"], mask, E_bins, on_device=a["generation_on_device"]) for k in kws]
     run.ids, run.errors = ids, errors
     run.verdict = S._guard_rule(eng, mask, E_bins, a["enforce_pauli"], a["pauli_warn_threshold"], a["pauli_error_threshold"])
     run.quiet_below = min([v for v in (a["pauli_warn_threshold"], a["pauli_error_threshold"]) if v is not None],

@@ -11,6 +11,11 @@ and only crosses PCIe at store points.  Additive keyword arguments (all optional
     error per step on true 2-D grids).
 ``device``
     torch device (default: current CUDA/HIP device).
+``generation_on_device``
+    ``True`` evaluates a ``custom`` generation expression inside the device subset of ``device_expr`` in a HIP kernel
+    instead of NumPy + an upload per step; its non-finite / negative check then arrives with the Pauli guard of the step
+    (up to ``Engine.GUARD_LAG`` steps late, before anything is stored).  Expressions outside the subset, every other
+    generation mode and the default ``False`` run exactly as before.
 
 Table builders and helpers the reference exports from ``qpsim.solver`` are re-exported here under
 the same names.
@@ -32,6 +37,7 @@ from .models import (
     SimulationParameters,
     normalize_collision_solver_name,
 )
+from . import device_expr
 from .safe_eval import compile_safe_expression
 from .timeloop import EnergyRun, Outputs, Schedule, energy_loop, scalar_loop
 
@@ -476,6 +482,7 @@ def run_2d_crank_nicolson(
     diffusion_scheme: str = "cn_exact",
     cn_rtol: float = 1e-13,
     device=None,
+    generation_on_device: bool = False,
 ):
     """Run the 2-D Crank-Nicolson diffusion (+ local collisions) time loop on the GPU.
 
@@ -485,6 +492,7 @@ def run_2d_crank_nicolson(
     mask, initial_field, store_every, n, tau_s_eff, tau_r_eff = _checked_run_arguments(
         mask, initial_field, diffusion_coefficient, dt, total_time, store_every, enable_diffusion, enable_recombination,
         enable_scattering, tau_0, tau_s, tau_r, external_generation, phonon_history_out)
+    device_expr.reset_run_stats()
 
     # Device grid = bounding box of the mask.  Interior cells keep their argwhere (row-major) order under the crop, so
     # the packed [NE, n] layout of every host-side array is unchanged; frames are still rebuilt on the full mask.  A
@@ -527,7 +535,7 @@ def run_2d_crank_nicolson(
                    _phonon_widths(eng, omega_bins, dE, [phonon_history_out]))
     run.ctab, run.floor = ctab, pauli_density_floor
     run.physics = (enable_recombination, enable_scattering, not freeze_phonon_dynamics)
-    run.generation = _Generation(external_generation, mask, E_bins)
+    run.generation = _Generation(external_generation, mask, E_bins, on_device=generation_on_device)
     run.verdict = _guard_rule(eng, mask, E_bins, enforce_pauli, pauli_warn_threshold, pauli_error_threshold)
 
     collisions = bool(enable_recombination or enable_scattering)
@@ -548,12 +556,25 @@ class _LoneRun(EnergyRun):
     ``physics`` = (recombination, scattering, phonon update), ``generation`` and ``verdict`` are set by the caller."""
     warned = False
 
+    def __init__(self, *args):
+        super().__init__(*args)
+        self.step = 0              # generate() is called once per step: the step its status tickets belong to
+        self.status: list = []     # (step, ticket) of the device-evaluated generation, read by guard_check
+
     def generate(self, t: float, dt_step: float) -> None:
         gen = self.generation
+        self.step += 1
         if not gen.active:
             return
         amount = gen.amount(t, dt_step)
-        if amount is None:                                       # custom mode: evaluated on the host (solver.py:918-962)
+        if amount is None:
+            launch = gen.device_step(t)
+            if launch is not None:                               # custom mode in the device subset: one kernel
+                self.status.append((self.step, self.eng.add_generation_expr(
+                    self.state, gen.window, [launch + (None,)], dt_step, 1, self.eng.d_flags)))
+                device_expr.count_steps(device=1)
+                return
+            device_expr.count_steps(host=1)                      # custom mode: evaluated on the host (solver.py:918-962)
             g_ext = gen.rates(t)
             if g_ext is not None:
                 self.eng.add_scaled(self.state, self.eng.upload_packed(g_ext), dt_step)
@@ -576,6 +597,7 @@ class _LoneRun(EnergyRun):
         return self.eng.pauli_stats_launch(self.state, self.ctab, self.floor)
 
     def guard_check(self, ticket, step: int, t: float) -> None:  # Pauli guard (solver.py:1296-1344)
+        _check_generation_status(self.eng, self.status, step)
         error, warning, self.warned = self.verdict(self.eng.pauli_stats_result(ticket), step, t, self.warned)
         if error is not None:
             raise ValueError(error)
@@ -584,15 +606,40 @@ class _LoneRun(EnergyRun):
             warnings.warn(warning, stacklevel=6)
 
 
-class _Generation:
-    """External generation of one problem during a run; a custom expression is compiled at its first use."""
+def _check_generation_status(eng, tickets: list, step: int) -> None:
+    """Reads the status of the device-evaluated generation of every step up to ``step`` (tickets are ``(step, ticket)`` in
+    step order) and raises what ``_validated_generation`` raises on the host path, non-finite before negative."""
+    while tickets and tickets[0][0] <= step:
+        for nonfinite, negative in eng.generation_status(tickets.pop(0)[1]):
+            rates = np.array([np.nan if nonfinite else (-1.0 if negative else 0.0)])
+            _validated_generation(rates, "custom", rates.shape)
 
-    def __init__(self, spec, mask, E_bins):
+
+class _Generation:
+    """External generation of one problem during a run; a custom expression is compiled at its first use.  With
+    ``on_device`` a custom expression is also compiled for the device evaluator; ``program`` stays None when it is
+    outside the device subset (or the mode is not custom), and the host path serves it."""
+
+    def __init__(self, spec, mask, E_bins, on_device: bool = False):
         self.spec, self.mask, self.E_bins = spec, mask, E_bins
         # the reference gates on the raw mode string (solver.py:1459)
         self.active = spec is not None and spec.mode != "none"
         self.constant = self.active and spec.mode.strip().lower() == "constant"
         self._compiled = None
+        self.program = None
+        if on_device and self.active and spec.mode.strip().lower() == "custom":
+            self.program = device_expr.compile_program(spec.custom_body.strip() or "0.0", spec.custom_params)
+            full = np.asarray(mask, dtype=bool)
+            # (ny_full, nx_full, row0, col0): the device grid is the bounding box of the mask (_crop_to_bounding_box)
+            self.window = full.shape + (int(np.flatnonzero(full.any(axis=1))[0]), int(np.flatnonzero(full.any(axis=0))[0]))
+
+    def device_step(self, t: float):
+        """(instruction words, slot table) of the step starting at ``t``, or None when the host path has to serve it."""
+        if self.program is None:
+            return None
+        words = self.program.instructions_for(t)
+        table = None if words is None else self.program.slot_table(self.E_bins, t)
+        return None if table is None else (words, table)
 
     def amount(self, t_start: float, dt_of_step: float):
         return _generation_amount(self.spec, t_start, dt_of_step)
