@@ -14,6 +14,9 @@ import os
 import numpy as np
 
 from . import _hip
+from . import collision_tables
+from .collision_tables import (antidiagonal_major, diagonal_major, onepass_tables, structured_bin_maps,  # noqa: F401
+                               tag_merged_bins)
 from .models import BoundaryCondition, EdgeSegment
 
 FLAG_XM, FLAG_XP, FLAG_YM, FLAG_YP, FLAG_ACTIVE = 1, 2, 4, 8, 16
@@ -174,77 +177,6 @@ def rect_side_terms(geom: CompiledGeometry):
     if any(v is None for v in xs + ys):
         return None
     return [xs[0], xs[1], ys[0], ys[1]], [xs[2], xs[3], ys[2], ys[3]]
-
-
-def structured_bin_maps(idx_diff, idx_sum, sign, allow_shared: bool = False):
-    """(diag_bin[NE], anti_bin[2NE-1]) if idx_diff[i][j] depends only on |i-j|, idx_sum[i][j] only on i+j and sign is
-    sign(i-j); None otherwise.  Unless ``allow_shared``, None is also returned when a phonon bin is fed by both a
-    diagonal (k >= 1) and an anti-diagonal (merged bins, e.g. when 2 E_min / dE is an integer)."""
-    idx_diff, idx_sum, sign = np.asarray(idx_diff), np.asarray(idx_sum), np.asarray(sign)
-    ne = idx_diff.shape[0]
-    if ne < 2:
-        return None
-    i, j = np.indices((ne, ne))
-    diag = idx_diff[np.arange(ne), 0]            # k = i - 0
-    anti = np.concatenate([idx_sum[0, :], idx_sum[1:, -1]])   # m = 0..2ne-2
-    if not (np.array_equal(idx_diff, diag[np.abs(i - j)]) and np.array_equal(idx_sum, anti[i + j])
-            and np.array_equal(sign, np.sign(i - j))):
-        return None
-    if np.unique(diag[1:]).size != ne - 1 or np.unique(anti).size != anti.size:
-        return None
-    used = np.concatenate([diag[1:], anti])
-    if not allow_shared and np.unique(used).size != used.size:
-        return None
-    return diag.astype(np.int32), anti.astype(np.int32)
-
-
-def diagonal_major(table: np.ndarray) -> np.ndarray:
-    """[..., ne, ne] -> [..., ne, ne] with out[k, i] = table[i, i - k] for k <= i < ne, 0 elsewhere: row k holds diagonal k
-    (the pairs with E_i - E_j = k dE) indexed by the higher bin - what a sweep along that diagonal reads is contiguous."""
-    t = np.asarray(table, dtype=np.float64)
-    ne = t.shape[-1]
-    out = np.zeros_like(t)
-    for k in range(ne):
-        i = np.arange(k, ne)
-        out[..., k, i] = t[..., i, i - k]
-    return out
-
-
-def antidiagonal_major(table: np.ndarray, scale: float = 1.0) -> np.ndarray:
-    """[..., ne, ne] -> [..., 2 ne - 1, ne] with out[m, i] = scale * table[i, m - i] for 0 <= m - i < ne, 0 elsewhere: row m
-    holds anti-diagonal m (the pairs with E_i + E_j fixed) indexed by one of its bins."""
-    t = np.asarray(table, dtype=np.float64)
-    ne = t.shape[-1]
-    out = np.zeros(t.shape[:-2] + (2 * ne - 1, ne))
-    for m in range(2 * ne - 1):
-        i = np.arange(max(0, m - ne + 1), min(ne, m + 1))
-        out[..., m, i] = scale * t[..., i, m - i]
-    return out
-
-
-def onepass_tables(ks0, kr0, nclass: int, ne: int):
-    """(ks0_diag, kr0_anti2) of the one-pass collision kernel (qpsim_hip.h): ``diagonal_major(ks0)`` [nclass, ne, ne] and
-    ``antidiagonal_major(kr0, 2.0)`` [nclass, 2 ne - 1, ne], one image per table - the image of class m is that of its table
-    alone, so a member's slice is what a lone call uploads.  None for a table that is None."""
-    ksd = None if ks0 is None else diagonal_major(np.asarray(ks0, dtype=np.float64).reshape(nclass, ne, ne))
-    kra = None if kr0 is None else antidiagonal_major(np.asarray(kr0, dtype=np.float64).reshape(nclass, ne, ne), 2.0)
-    return ksd, kra
-
-
-def tag_merged_bins(diag, anti):
-    """(diag, anti, n_merged): entries of a phonon bin fed by both a diagonal k >= 1 and an anti-diagonal m get
-    (slot + 1) << 16 added, slot numbering the merged bins (what the register collision kernels expect, qpsim_hip.h)."""
-    diag, anti = np.array(diag, dtype=np.int32), np.array(anti, dtype=np.int32)
-    where = {int(b): m for m, b in enumerate(anti)}
-    slots = 0
-    for k in range(1, diag.size):
-        m = where.get(int(diag[k]))
-        if m is not None:
-            tag = (slots + 1) << 16
-            diag[k] |= tag
-            anti[m] |= tag
-            slots += 1
-    return diag, anti, slots
 
 
 class RectPlan:
@@ -856,114 +788,23 @@ class Engine:
         = C, class m = the cells of member m).  The register kernels read them for NE = 4 ... 16 when a member's cell count
         is a multiple of 64, the one-pass kernel for NE = 30, 32, 40, 50 when it is a multiple of 256 (the handle then
         carries ``ks0_diag`` / ``kr0_anti2`` per member and reports ``kernel == "register"``); other shapes and sizes run
-        the one-wave-per-pixel kernel through the class map."""
-        torch = self.torch
-        up = lambda a, dt: None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.device)  # noqa: E731
-        rho = np.atleast_2d(np.asarray(rho, dtype=np.float64))
-        nclass, ne = rho.shape
-        h = {"kr0": up(None if kr0 is None else np.asarray(kr0).reshape(nclass, ne, ne), np.float64),
-             "ks0": up(None if ks0 is None else np.asarray(ks0).reshape(nclass, ne, ne), np.float64),
-             "rho": up(rho, np.float64), "idx_diff": up(idx_diff, np.int32), "idx_sum": up(idx_sum, np.int32),
-             "sign": up(sign, np.int8), "cls": None, "ne": ne, "nclass": nclass}
-        nw = int(max(np.max(idx_diff), np.max(idx_sum))) + 1
-        if member_classes:
-            if nclass != int(members):
-                raise ValueError("member classes need one table set per member")
-            h["cls"] = up(np.repeat(np.arange(nclass, dtype=np.int32), self.ncell), np.int32)
-            gap_params = None
-            if kernel == "auto" and os.environ.get("QPSIM_MEMBER_TABLES", "1") == "0":      # A/B timing: class-map kernels
-                kernel = "wave"
-        elif nclass > 1:
-            if cls_packed is None:
-                raise ValueError("cls is required for more than one gap class")
-            full = np.zeros(self.ncell, dtype=np.int32)
-            full[self.mask_flat] = np.asarray(cls_packed, dtype=np.int32)
-            h["cls"] = up(np.tile(full, int(members)), np.int32)
-        h["nw"] = nw
-        h["diag_bin"] = h["anti_bin"] = None
-        h["merged_slots"] = 0
-        structure = structured_bin_maps(idx_diff, idx_sum, sign, allow_shared=True)
-        shared = structure is not None and structured_bin_maps(idx_diff, idx_sum, sign) is None
-        if structure is not None and kernel != "wave_unstructured":
-            diag, anti = (np.array(a, dtype=np.int32) for a in structure)
-            if shared:
-                # a phonon bin fed by diagonal k AND anti-diagonal m: both table entries carry (slot + 1) << 16 so that the
-                # register kernels park the diagonal's sums in scratch slot `slot` until the anti-diagonal finalises the bin
-                diag, anti, h["merged_slots"] = tag_merged_bins(diag, anti)
-            h["diag_bin"], h["anti_bin"] = up(diag, np.int32), up(anti, np.int32)
-        # the register and wave kernels visit each unordered pair once (K^r_0, K^s_0 and the bin maps of the reference are
-        # symmetric, sign antisymmetric: solver.py:463-490, 668-683); caller-supplied tables of the step API that are not
-        # run the generic kernel, which reads (i, j) and (j, i) separately
-        sym = lambda a: a is None or np.array_equal(np.asarray(a), np.swapaxes(np.asarray(a), -1, -2))  # noqa: E731
-        symmetric = (sym(kr0 if kr0 is None else np.asarray(kr0).reshape(nclass, ne, ne))
-                     and sym(ks0 if ks0 is None else np.asarray(ks0).reshape(nclass, ne, ne))
-                     and sym(idx_diff) and sym(idx_sum)
-                     and np.array_equal(np.asarray(sign), -np.asarray(sign).T))
-        h["symmetric"] = bool(symmetric)
-        if (not allow_fast or not symmetric) and kernel == "auto":
-            kernel = "generic"
-        flag_bits = ({"auto": 0, "generic": 1, "wave": 2, "wave_unstructured": 2}[kernel] | (4 if shared else 0)
-                     | (8 if member_classes else 0))
-        if kernel == "wave_unstructured":
-            kernel = "wave"
-        wave_ok = ne <= 64 and nw <= 192
-        h["gap_sq"] = h["kr_amp"] = h["ks_amp"] = h["pair_inv"] = None
-        classes_ok = False
-        if (nclass > 1 and gap_params is not None and structure is not None
-                and bool(self.lib.qp_collision_register_kernel_classes(ne))):
-            from .tables import KB_UEV_PER_K
-            E = np.asarray(gap_params["E"], dtype=np.float64)
-            kTc = KB_UEV_PER_K * float(gap_params["T_c"])
-            psum, pdiff = E[:, None] + E[None, :], E[:, None] - E[None, :]
-            h["pair_inv"] = up(1.0 / np.maximum(E[:, None] * E[None, :], 1e-30), np.float64)
-            h["gap_sq"] = up(np.asarray(gap_params["gaps"], dtype=np.float64) ** 2, np.float64)
-            if kr0 is not None:
-                h["kr_amp"] = up((1.0 / float(gap_params["tau_r"])) * (psum / kTc) ** 2 / kTc, np.float64)
-            if ks0 is not None:
-                ksa = (1.0 / float(gap_params["tau_s"])) * pdiff ** 2 / kTc ** 3
-                np.fill_diagonal(ksa, 0.0)
-                h["ks_amp"] = up(ksa, np.float64)
-            classes_ok = True
-        # member classes: the register kernels' member-table form where it exists, decided per call by the member's cell
-        # count (the merged-bin stash is sized for it either way)
-        members_ok = bool(member_classes and self.lib.qp_collision_member_tables_available(ne))
-        # ... and at the one-pass sizes that kernel, whose 256-pixel blocks each stage the tables of one member
-        members_onepass = bool(member_classes and kernel == "auto" and structure is not None and symmetric
-                               and self.ncell % 256 == 0 and self.lib.qp_collision_onepass_available(ne))
-        h["member_classes"] = bool(member_classes)
-        h["kernel"] = ("generic" if (kernel == "generic" or not wave_ok) else
-                       "register" if (kernel == "auto" and structure is not None
-                                      and ((members_ok or members_onepass) if member_classes else (nclass == 1 or classes_ok))
-                                      and bool(self.lib.qp_collision_register_kernel_available(ne))) else "wave")
-        h["fast"] = h["kernel"] != "generic"      # no accumulator planes needed
-        # one-pass kernel (ne = 30, 32, 40, 50): the kernel tables once more in (anti)diagonal-major order (qpsim_hip.h)
-        h["ks0_diag"] = h["kr0_anti2"] = None
-        # (member classes: one image per member)
-        if (h["kernel"] == "register" and (nclass == 1 or members_onepass) and symmetric
-                and bool(self.lib.qp_collision_onepass_available(ne))):
-            ksd, kra = onepass_tables(ks0, kr0, nclass, ne)
-            h["ks0_diag"] = up(ksd if nclass > 1 or ksd is None else ksd[0], np.float64)
-            h["kr0_anti2"] = up(kra if nclass > 1 or kra is None else kra[0], np.float64)
-        # consecutive half-steps of neighbouring Strang steps in one pass (qp_collision_double_step_guarded)
-        h["pair"] = bool(h["kernel"] == "register" and (nclass == 1 or members_ok) and structure is not None and not shared
-                         and symmetric
-                         and kernel == "auto" and self.lib.qp_collision_pair_available(ne)
-                         and os.environ.get("QPSIM_COLL_PAIR", "1") != "0")
-        h["struct"] = _hip.CollisionTables.make(ne, nw, nclass, _ptr(h["kr0"]), _ptr(h["ks0"]), _ptr(h["rho"]),
-                                           _ptr(h["idx_diff"]), _ptr(h["idx_sum"]), _ptr(h["sign"]), _ptr(h["cls"]),
-                                           _ptr(h["diag_bin"]), _ptr(h["anti_bin"]), flag_bits,
-                                           _ptr(h["gap_sq"]), _ptr(h["kr_amp"]), _ptr(h["ks_amp"]), _ptr(h["pair_inv"]),
-                                           _ptr(h["ks0_diag"]), _ptr(h["kr0_anti2"]))
+        the one-wave-per-pixel kernel through the class map.
+
+        Every rule is ``collision_tables.plan_collision_tables`` (host only); this method uploads its arrays and fills the
+        struct.  ``handle["kernel"]`` is the family the table set can reach (``collision_tables.CollisionPlan``)."""
+        plan = collision_tables.plan_collision_tables(self.lib, self.ncell, self.mask_flat, kr0, ks0, rho, idx_diff, idx_sum,
+                                                      sign, cls_packed, allow_fast, kernel, gap_params, members,
+                                                      member_classes)
+        h = {name: None if a is None else self.torch.as_tensor(a, device=self.device) for name, a in plan.arrays.items()}
+        h.update(ne=plan.ne, nclass=plan.nclass, nw=plan.nw, merged_slots=plan.merged_slots, symmetric=plan.symmetric,
+                 member_classes=plan.member_classes, kernel=plan.kernel, fast=plan.fast, pair=plan.pair,
+                 struct=plan.struct({name: _ptr(t) for name, t in h.items()}))
         return h
 
-    def _collision_scratch(self, tables, nc: int, en_r, en_s, update_phonons):
-        """What a collision call over ``nc`` pixels needs beside its planes: the phonon accumulator planes of the kernels
-        that are not ``fast``, the merged-bin stash of the register kernels, or None."""
-        planes = 0
-        if update_phonons and (en_r or en_s) and not tables["fast"]:
-            planes = tables["nw"]
-        if tables["kernel"] == "register" and tables["merged_slots"] and update_phonons and en_r and en_s:
-            planes = tables["merged_slots"]
+    def collision_scratch(self, tables, nc: int, en_r, en_s, update_phonons):
+        """What a collision call over ``nc`` pixels needs beside its planes (``collision_tables.scratch_planes``): the phonon
+        accumulator planes of the kernels that are not ``fast``, the merged-bin stash of the register kernels, or None."""
+        planes = collision_tables.scratch_planes(tables, en_r, en_s, update_phonons)
         return self.scratch("coll_acc", 2 * planes * nc) if planes else None
 
     def _guard_workspace(self, nc: int, min_bytes: int = 0):
@@ -979,7 +820,7 @@ class Engine:
                 flags=None):
         """One collision update; ``ncell`` / ``flags`` override the engine's grid (ensembles: members x cells)."""
         nc = self.ncell if ncell is None else int(ncell)
-        acc = self._collision_scratch(tables, nc, en_r, en_s, update_phonons)
+        acc = self.collision_scratch(tables, nc, en_r, en_s, update_phonons)
         _hip.check(self.lib.qp_collision_step(C.byref(tables["struct"]), _ptr(self.d_flags if flags is None else flags), nc, _ptr(state),
                                               _ptr(state_out), _ptr(phonon), _ptr(acc), float(dE), float(dt),
                                               int(bool(en_r)), int(bool(en_s)), int(bool(update_phonons)), self.stream),
@@ -991,7 +832,7 @@ class Engine:
         single-pass register kernels reduce the statistics of the new densities while they are still in registers.
         Returns a ticket for ``pauli_stats_result`` (asynchronous read-back, as ``pauli_stats_launch``)."""
         nc = self.ncell if ncell is None else int(ncell)
-        acc = self._collision_scratch(tables, nc, en_r, en_s, update_phonons)
+        acc = self.collision_scratch(tables, nc, en_r, en_s, update_phonons)
         ws = self._guard_workspace(nc)
         hv, hi, ev = self._guard_slot()
         _hip.check(self.lib.qp_collision_step_guarded(
@@ -1201,7 +1042,7 @@ class Engine:
                                 ncell_member: int, members: int, flags):
         """``collide_guarded`` over an ensemble with the guard reduced per member (``qp_collision_step_guarded_members``)."""
         nc = int(ncell_member) * int(members)
-        acc = self._collision_scratch(tables, nc, en_r, en_s, update_phonons)
+        acc = self.collision_scratch(tables, nc, en_r, en_s, update_phonons)
 
         def call(ws, vals, idx):
             _hip.check(self.lib.qp_collision_step_guarded_members(
@@ -1213,7 +1054,7 @@ class Engine:
     @staticmethod
     def pair_members_supported(tables, ncell_member: int, members: int) -> bool:
         """Whether ``qp_collision_double_step_guarded_members`` accepts this ensemble (else two calls per step pair)."""
-        return bool(tables.get("pair")) and ncell_member % 64 == 0 and ncell_member * members < (1 << 28)
+        return collision_tables.pair_members_supported(tables, ncell_member, members)
 
     def collide_pair_guarded_members(self, tables, state, state_out, phonon, dE, dt_first, dt_second, gen_amount, en_r,
                                      en_s, update_phonons, floor: float, ncell_member: int, members: int, flags):

@@ -118,9 +118,9 @@ def _tab(s, family, kernel):
 
 def _route(s, tab, combo):
     """The library's answer for the call `Engine.collide` makes with these tables and switches."""
+    from qpsim_amd.collision_tables import scratch_planes
     en_r, en_s, upd = combo
-    scratch = (upd and (en_r or en_s) and not tab["fast"]) or (tab["kernel"] == "register" and tab["merged_slots"] > 0
-                                                              and upd and en_r and en_s)
+    scratch = scratch_planes(tab, en_r, en_s, upd) > 0
     return s["eng"].lib.qp_collision_route(C.byref(tab["struct"]), s["eng"].ncell, int(en_r), int(en_s), int(upd), int(scratch))
 
 
@@ -360,3 +360,44 @@ def test_rate_times_step_regimes_on_both_sides_of_the_small_x_switch(O, monkeypa
     for i, (name, got, ref, tol) in enumerate((("state", got_s, ref_s, tol_s), ("phonons", got_p, ref_p, tol_p))):
         check(got, ref, s["level"], tol, f"{tag} {name} vs oracle", rule=X87_RULE.get((family, "regimes", name), ()), ref64=ref,
               ref80=lambda i=i: _oracle(O, s, family, combo, dt, np.longdouble)[i])
+
+
+# ------------------------------------------------------------------------------------------------ 3. upload of a plan
+@pytest.mark.parametrize("kind,ne,cells", [("plain", 12, 64), ("member", 30, 256), ("gap", 12, 64)])
+def test_handle_is_the_plan_uploaded_once(kind, ne, cells):
+    """Every tensor of the handle is the plan's array, bit for bit, and the struct holds its address (no kernel runs)."""
+    from qpsim_amd import _hip as H
+    from qpsim_amd import tables as T
+    from qpsim_amd.collision_tables import ARRAY_NAMES, plan_collision_tables
+    from qpsim_amd.engine import CompiledGeometry, Engine, link_flags
+    mask = np.ones((cells // 64, 64), dtype=bool)
+    z = np.zeros(mask.shape)
+    eng = Engine(CompiledGeometry(mask, 1.0, link_flags(mask), z, z, z, z))
+    E, _ = T.build_energy_grid(180.0, 1.0, unmerged_fmax(ne), ne)
+    maps = T.build_phonon_frequency_map(E)[1:]
+    kr = np.stack([T.recombination_kernel_base(E, g, 500.0, 1.2) for g in GAPS[:3]])
+    ks = np.stack([T.scattering_kernel_base(E, g, 400.0, 1.2) for g in GAPS[:3]])
+    rho = np.stack([T.dynes_density_of_states(E, g, 0.1) for g in GAPS[:3]])
+    if kind == "plain":
+        args, kw = (kr[:1], ks[:1], rho[:1], *maps), {}
+    elif kind == "member":
+        args, kw = (kr, ks, rho, *maps), dict(members=3, member_classes=True)
+    else:
+        args = (kr, ks, rho, *maps, np.arange(eng.ncell) % 3)
+        kw = dict(gap_params=dict(E=E, gaps=GAPS[:3], tau_r=500.0, tau_s=400.0, T_c=1.2))
+    plan = plan_collision_tables(eng.lib, eng.ncell, eng.mask_flat, *args, **kw)
+    tab = eng.make_collision_tables(*args, **kw)
+    assert tab["kernel"] == plan.kernel == "register"
+    assert (plan.arrays["kr0_anti2"] is not None) == (kind == "member") and (plan.arrays["gap_sq"] is not None) == (kind == "gap")
+    pointers = [name for name, ctype in H.CollisionTables._fields_ if ctype is H.c_dp]
+    assert pointers == list(ARRAY_NAMES)
+    for name in ARRAY_NAMES:
+        want, got = plan.arrays[name], tab[name]
+        if want is None:
+            assert got is None and not getattr(tab["struct"], name)
+            continue
+        back = got.cpu().numpy()
+        assert back.dtype == want.dtype and back.shape == want.shape and back.tobytes() == want.tobytes(), name
+        assert getattr(tab["struct"], name) == got.data_ptr(), name
+    assert (tab["struct"].ne, tab["struct"].nw, tab["struct"].nclass, tab["struct"].flags) == (
+        plan.ne, plan.nw, plan.nclass, plan.flag_bits)
