@@ -172,6 +172,14 @@ typedef struct qp_collision_tables {
  * generic kernel through cls, and the double half-step call returns QP_ERR_UNSUPPORTED.  gap_sq / kr_amp / ks_amp /
  * pair_inv are not used with this flag. */
 #define QP_COLL_MEMBER_CLASSES 8u
+/* Padded bins (opt-in): where qp_collision_padded_ceiling(ne) = C != 0, diag_bin / anti_bin are given, no FORCE bit is set,
+ * there is one class (or member classes under the 256-cell rule above) and the image of every effective process is present,
+ * the one-pass kernel instantiated for C bins runs on the ne live bins.  `ne`, `nw` and every array keep describing the LIVE
+ * size: ks0_diag / kr0_anti2 are the [ne][ne] / [2ne-1][ne] images (one per class with QP_COLL_MEMBER_CLASSES); the kernel
+ * lays them into its C-sized LDS image itself and neither reads nor writes a state, phonon or scratch plane that the live
+ * size does not have.  Sizes with a kernel of their own, ne <= 16, ne >= 51, gap classes and the double half-step call are
+ * not affected by the flag. */
+#define QP_COLL_PAD_BINS 16u
 
 /*
  * One local coupled quasiparticle-phonon collision update of every interior cell
@@ -234,6 +242,10 @@ int qp_collision_register_kernel_classes(int32_t ne);
 /* 1 when the single-pass and the double half-step register kernels are instantiated in their member-table form
  * (QP_COLL_MEMBER_CLASSES) for `ne`: ne = 4 ... 16. */
 int qp_collision_member_tables_available(int32_t ne);
+/* The size C of the one-pass kernel that serves `ne` live bins under QP_COLL_PAD_BINS: 30 for ne = 17, 19, 21-23, 25-29;
+ * 32 for 31; 40 for 33-39; 50 for 41-49; 0 for every size with a one-pass or register kernel of its own, for ne <= 16 and
+ * for ne >= 51. */
+int qp_collision_padded_ceiling(int32_t ne);
 
 /* The kernel family qp_collision_step (and the step inside the guarded calls) runs for these tables, cell count and
  * switches; have_scratch: whether ph_scratch would be non-NULL.  Launches nothing and reads only the struct itself (its
@@ -247,7 +259,8 @@ typedef enum qp_collision_route_kind {
   QP_ROUTE_REGISTER_CLASSES = 4, /* register kernel, gap classes */
   QP_ROUTE_WAVE = 5,             /* one wave per pixel */
   QP_ROUTE_GENERIC = 6,          /* one thread per cell, any table */
-  QP_ROUTE_COPY = 7              /* no effective process at a register-kernel size: n' = max(n, 0) */
+  QP_ROUTE_COPY = 7,             /* no effective process at a register-kernel size: n' = max(n, 0) */
+  QP_ROUTE_ONEPASS_PADDED        /* (8) one-pass kernel of the ceiling size on fewer live bins; only with QP_COLL_PAD_BINS */
 } qp_collision_route_kind;
 int qp_collision_route(const qp_collision_tables* t, int64_t ncell, int enable_recombination, int enable_scattering,
                        int update_phonons, int have_scratch);

@@ -161,6 +161,12 @@ Route collision_route(const qp_collision_tables& t, long ncell, bool en_r, bool 
   if (reg && member_classes && collision_onepass_supported(t.ne) && (s || r) && (!s || t.ks0_diag) && (!r || t.kr0_anti2) &&
       onepass_enabled() && (ncell / t.nclass) % 256 == 0)
     return QP_ROUTE_ONEPASS;
+  // padded bins (opt-in, QP_COLL_PAD_BINS): a size without a kernel of its own runs the one-pass kernel of its ceiling size
+  // on the live bins; one class, or member classes under the same 256-cell rule.  Everything else falls through as without
+  // the flag
+  if ((t.flags & QP_COLL_PAD_BINS) && reg && (t.nclass == 1 || (member_classes && (ncell / t.nclass) % 256 == 0)) &&
+      (s || r) && (!s || t.ks0_diag) && (!r || t.kr0_anti2) && qp_collision_padded_ceiling(t.ne) != 0 && onepass_enabled())
+    return QP_ROUTE_ONEPASS_PADDED;
   // gap classes with the separable kernel tables: the one-pass kernel where it exists ...
   if (reg && gap_classes && t.cls && t.gap_sq && t.pair_inv) {
     if (collision_onepass_classes_supported(t.ne) && t.nclass <= kOnePassMaxClasses && (s || r) && (!s || t.ks_amp) &&
@@ -263,6 +269,7 @@ static int collision_step_impl(const char* who, const qp_collision_tables* t, co
   switch (route) {
     case QP_ROUTE_ONEPASS:
     case QP_ROUTE_ONEPASS_CLASSES:
+    case QP_ROUTE_ONEPASS_PADDED:
       qp::collision_onepass_dispatch(route, *t, c);
       break;
     case QP_ROUTE_REGISTER:
@@ -365,6 +372,13 @@ extern "C" int qp_collision_pair_available(int32_t ne) { return qp::collision_pa
 extern "C" int qp_collision_member_tables_available(int32_t ne) { return qp::collision_member_tables_supported(ne); }
 
 extern "C" int qp_collision_onepass_available(int32_t ne) { return qp::collision_onepass_supported(ne); }
+
+// The one-pass kernel that serves `ne` live bins under QP_COLL_PAD_BINS: the smallest instantiated size above ne, for the
+// sizes between 17 and 49 that have neither a one-pass nor a register kernel of their own
+extern "C" int qp_collision_padded_ceiling(int32_t ne) {
+  if (ne <= 16 || ne >= 50 || qp::collision_onepass_supported(ne) || qp::collision_fast_supported(ne)) return 0;
+  return ne < 30 ? 30 : ne < 32 ? 32 : ne < 40 ? 40 : 50;
+}
 
 // 1 when the gap-class variant (separable kernel tables, qp_collision_tables::gap_sq ...) exists as well
 extern "C" int qp_collision_register_kernel_classes(int32_t ne) { return qp::collision_fast_classes_supported(ne); }

@@ -54,9 +54,15 @@ struct OnePassView {
   int nclass;              // gap-class form (PARAM kernels): base.cls, gap_sq, kr_amp, ks_amp, pair_inv, rho[nclass][NE]
   unsigned member_blocks;  // member tables (the other kernels): blocks per ensemble member - block b stages table set
                            // b / member_blocks of kr0, ks0, rho, ksd, kra2; 0: one shared set
+  int ne_live;             // TRIM kernels: the live size ne <= NE every table, bin map and plane count above belongs to
 };
 
 constexpr int kOnePassThreads = 256;
+
+// TRIM kernels: the smallest live size the kernel of ceiling size `ne` is launched with - one above the next smaller
+// instantiated size (qp_collision_padded_ceiling: 30 serves 17 ... 29, 32: 31, 40: 33 ... 39, 50: 41 ... 49).  Bins below it
+// are live in every launch, so their guards fold away at compile time; the dispatcher holds the launch to the range.
+__host__ __device__ constexpr int onepass_trim_min(int ne) { return ne == 30 ? 17 : ne == 32 ? 31 : ne == 40 ? 33 : ne == 50 ? 41 : ne; }
 
 // compact (anti)diagonal-major order of the unordered pairs phase 2 visits: diagonal k >= 1 holds (i, i - k) for
 // i = k .. NE-1, anti-diagonal m holds (i, m - i) for i = ceil(m / 2) .. min(m, NE-1)
@@ -97,8 +103,27 @@ struct OnePassLds {
   static constexpr int anti_at(int m, int i) { return PARAM ? onepass_anti_start(NE, m) + (i - onepass_anti_lo(m)) : m * NE + i; }
 };
 
+// TRIM (padded bins, QP_ROUTE_ONEPASS_PADDED): the kernel of the ceiling size NE on ne = w.ne_live < NE live bins.  The
+// caller's tables, bin maps and planes all have the live size; nothing is padded outside the kernel.
+//   staging  the rows of ks0, kr0, rho, ksd, kra2 are read with stride ne (member stride ne ne, (2 ne - 1) ne) and laid into
+//            the NE-strided LDS image, every other entry of the image is 0.0; the offset tables hold, for a diagonal
+//            k >= ne or an anti-diagonal m > 2 ne - 2, the offset of the LAST LIVE one (diag_bin / anti_bin are not read
+//            past their live extent, and a load through such an entry reads a plane that exists)
+//   reads    n_i of a pad bin is loaded from plane ne - 1 (scalar min) and replaced by 0.0; with rho = 0 and K = 0 from the
+//            image, q = 0 and every product a pad bin enters is an exact +0.0 added to a non-negative accumulator: the
+//            sums over the live pairs keep their order and their bits.  The load streams (n planes, the Pk / Pm windows,
+//            the Pq rings) stay unconditional - a guard per load would serialise them.  A pad (anti)diagonal's window value
+//            is the clamped plane's, NOT zeroed: it only ever multiplies K = 0 of a pair whose target is a pad bin (the
+//            partner steps j >= ne that would pair it with a live target are skipped) and that target is never stored;
+//            a select at the load site would wait for the load in the step that issues it and undo the prefetch
+//   skipped  target blocks with lo >= ne, partner steps j >= ne, diagonals k >= ne and anti-diagonals m > 2 ne - 2:
+//            wave-uniform branches (ne is a kernel argument) around whole blocks / steps / diagonals - only where the
+//            index can be a pad one, i.e. from onepass_trim_min(NE) on: everything below is the native code
+//   writes   state_out planes >= ne (also of cells outside the mask), phonon planes and stash planes of pad (anti)diagonals
+//            are never written: the stores sit behind the same branches
+// TRIM = false compiles to what it compiled to without the flag: every addition is under a compile-time condition.
 template <int NE, int TB, bool USE_S, bool USE_R, bool UPD, int PF, int WAVES, int G = 7, int G2 = 4, int PF2 = 12,
-          bool PARAM = false>
+          bool PARAM = false, bool TRIM = false>
 __global__ void __launch_bounds__(kOnePassThreads) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))
 collision_onepass_kernel(OnePassView w, const uint8_t* __restrict__ flags, long ncell, const double* __restrict__ sin_,
                          double* __restrict__ sout, double* __restrict__ ph, double dE, double dt) {
@@ -113,10 +138,24 @@ collision_onepass_kernel(OnePassView w, const uint8_t* __restrict__ flags, long 
   // Member tables: all cells of a block belong to one ensemble member (the route sees to it), so the block stages that
   // member's tables and everything behind the staging loops is the kernel of a lone call - bit-equal results.  Scalar code.
   const long mb = (!PARAM && w.member_blocks) ? (long)(blockIdx.x / w.member_blocks) : 0L;
+  static_assert(!(TRIM && PARAM), "gap classes are not trimmed");
+  const int ne = TRIM ? w.ne_live : NE;      // live bins (wave-uniform; the constant NE unless TRIM)
+  constexpr int LMIN = onepass_trim_min(NE);  // ne >= LMIN: a bin, partner or diagonal below it needs no run-time test
+  constexpr int AMIN = 2 * LMIN - 2;          // ... and an anti-diagonal up to it neither
 
   // ---- stage the phase-1 tables ------------------------------------------------------------------------------------------
   {
     const int tid = threadIdx.x;
+    if constexpr (TRIM) {      // live rows (stride ne) into the NE-strided image, zeros everywhere else
+      const long mt = mb * (ne * ne);
+      for (int e = tid; e < NE * NE; e += kOnePassThreads) {
+        const int row = e / NE, col = e % NE;
+        const bool in = row < ne && col < ne;
+        if (USE_S) lds[L::kKs + e] = in ? t.ks0[mt + row * ne + col] : 0.0;
+        if (USE_R) lds[L::kKr + e] = in ? t.kr0[mt + row * ne + col] : 0.0;
+      }
+      if (tid < NE) lds[L::kRho + tid] = tid < ne ? t.rho[mb * ne + tid] : 0.0;
+    } else {
     const long mt = mb * (NE * NE);
     if (USE_S) for (int e = tid; e < NE * NE; e += kOnePassThreads) lds[L::kKs + e] = PARAM ? t.ks_amp[e] : t.ks0[mt + e];
     if (USE_R) for (int e = tid; e < NE * NE; e += kOnePassThreads) lds[L::kKr + e] = PARAM ? t.kr_amp[e] : t.kr0[mt + e];
@@ -126,18 +165,30 @@ collision_onepass_kernel(OnePassView w, const uint8_t* __restrict__ flags, long 
     } else if (tid < NE) {
       lds[L::kRho + tid] = t.rho[mb * NE + tid];
     }
-    // byte offsets of the phonon planes as 64-bit integers in the same array
-    if (USE_S && tid < NE) reinterpret_cast<long*>(lds)[L::kOffD + tid] = (long)bin_of(t.diag_bin[tid]) * ncell * 8;
-    if (USE_R && tid < 2 * NE - 1) reinterpret_cast<long*>(lds)[L::kOffA + tid] = (long)bin_of(t.anti_bin[tid]) * ncell * 8;
+    }
+    // byte offsets of the phonon planes as 64-bit integers in the same array (TRIM: a pad entry repeats the last live one)
+    const int td = TRIM ? (tid < ne - 1 ? tid : ne - 1) : tid, ta = TRIM ? (tid < 2 * ne - 2 ? tid : 2 * ne - 2) : tid;
+    if (USE_S && tid < NE) reinterpret_cast<long*>(lds)[L::kOffD + tid] = (long)bin_of(t.diag_bin[td]) * ncell * 8;
+    if (USE_R && tid < 2 * NE - 1) reinterpret_cast<long*>(lds)[L::kOffA + tid] = (long)bin_of(t.anti_bin[ta]) * ncell * 8;
   }
   __syncthreads();
 
   double n[NE];
 #pragma unroll
-  for (int i = 0; i < NE; ++i) n[i] = __builtin_nontemporal_load(&(sin_ + (long)i * ncell)[p]);
+  for (int i = 0; i < NE; ++i) {
+    const int plane = (TRIM && i >= LMIN && i >= ne) ? ne - 1 : i;      // TRIM: a pad bin re-reads the last live plane
+    n[i] = __builtin_nontemporal_load(&(sin_ + (long)plane * ncell)[p]);
+  }
+  if constexpr (TRIM) {       // pad bins: every load above read a live plane; the lane sees n = 0
+#pragma unroll
+    for (int i = LMIN; i < NE; ++i) n[i] = i < ne ? n[i] : 0.0;
+  }
   if (in_grid && !live) {     // cells outside the mask pass through unchanged
 #pragma unroll
-    for (int i = 0; i < NE; ++i) (sout + (long)i * ncell)[p] = n[i];
+    for (int i = 0; i < NE; ++i) {
+      if (TRIM && i >= LMIN && i >= ne) continue;      // (continue, not break: a run-time exit would keep the loop from unrolling)
+      (sout + (long)i * ncell)[p] = n[i];
+    }
   }
   const char* const lane_ph = reinterpret_cast<const char*>(ph + p);      // this lane's cell in plane 0
   // gap classes: the lane's row of the rho table and -gap^2 (K_s = amp max(1 - gap^2 pair_inv, 0), K_r = amp (1 + gap^2 pair_inv))
@@ -155,6 +206,7 @@ collision_onepass_kernel(OnePassView w, const uint8_t* __restrict__ flags, long 
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const int lo = b * TB, hi = lo + TB < NE ? lo + TB : NE;
+    if (TRIM && lo >= LMIN && lo >= ne) continue;   // the block holds pad bins only
     double ga[TB], la[TB];
 #pragma unroll
     for (int x = 0; x < TB; ++x) { ga[x] = 0.0; la[x] = 0.0; }
@@ -177,6 +229,7 @@ collision_onepass_kernel(OnePassView w, const uint8_t* __restrict__ flags, long 
           }
         }
         if (j < 0) continue;
+        if (TRIM && j >= LMIN && j >= ne) continue;  // pad partners: zero contributions (the window loads above stay unconditional)
         const double nj = n[j];
         const double qj = fmax(QP_RHO(j) - nj, 0.0);
         // G targets at a time: their K P products, then their K (1 + P) sums, then the four updates of each - three
@@ -266,6 +319,7 @@ collision_onepass_kernel(OnePassView w, const uint8_t* __restrict__ flags, long 
           if (jn >= 1 && jn < NE) Pm[hi - 1 + jn] = QP_PLANE_LOAD(L::kOffA + hi - 1 + jn);
         }
         if (j < 0) continue;
+        if (TRIM && j >= LMIN && j >= ne) continue;  // pad partners: zero contributions (the window loads above stay unconditional)
         const double nj = n[j];
         const double qj = fmax(QP_RHO(j) - nj, 0.0);
 #pragma unroll
@@ -337,6 +391,7 @@ collision_onepass_kernel(OnePassView w, const uint8_t* __restrict__ flags, long 
     for (int x = 0; x < TB; ++x) {
       const int i = lo + x;
       if (i >= hi) continue;
+      if (TRIM && i >= LMIN && i >= ne) continue;    // pad targets are not stored
       const double qi = fmax(QP_RHO(i) - n[i], 0.0);
       __builtin_nontemporal_store(relax_update_f<false>(n[i], scale * qi * ga[x], scale * la[x], dt, ec),
                                   &(sout + (long)i * ncell)[p]);
@@ -373,13 +428,25 @@ collision_onepass_kernel(OnePassView w, const uint8_t* __restrict__ flags, long 
               lds[L::kPia + at] = t.pair_inv[i * NE + (m - i)];
             }
           }
+      } else if constexpr (TRIM) {      // the live [ne][ne] / [2 ne - 1][ne] images into the NE-strided ones, zeros elsewhere
+        if (USE_S)
+          for (int e = tid; e < NE * NE; e += kOnePassThreads) {
+            const int k = e / NE, i = e % NE;
+            lds[L::kKsd + e] = (k < ne && i < ne) ? w.ksd[mb * (ne * ne) + k * ne + i] : 0.0;
+          }
+        if (USE_R)
+          for (int e = tid; e < (2 * NE - 1) * NE; e += kOnePassThreads) {
+            const int m = e / NE, i = e % NE;
+            lds[L::kKra + e] = (m < 2 * ne - 1 && i < ne) ? w.kra2[mb * ((2 * ne - 1) * ne) + m * ne + i] : 0.0;
+          }
       } else {
         if (USE_S) for (int e = tid; e < NE * NE; e += kOnePassThreads) lds[L::kKsd + e] = w.ksd[mb * (NE * NE) + e];
         if (USE_R)
           for (int e = tid; e < (2 * NE - 1) * NE; e += kOnePassThreads) lds[L::kKra + e] = w.kra2[mb * ((2 * NE - 1) * NE) + e];
       }
-      if (USE_S && tid < NE) reinterpret_cast<long*>(lds)[L::kOffD2 + tid] = (long)bin_of(t.diag_bin[tid]) * ncell * 8;
-      if (USE_R && tid < 2 * NE - 1) reinterpret_cast<long*>(lds)[L::kOffA2 + tid] = (long)bin_of(t.anti_bin[tid]) * ncell * 8;
+      const int td = TRIM ? (tid < ne - 1 ? tid : ne - 1) : tid, ta = TRIM ? (tid < 2 * ne - 2 ? tid : 2 * ne - 2) : tid;
+      if (USE_S && tid < NE) reinterpret_cast<long*>(lds)[L::kOffD2 + tid] = (long)bin_of(t.diag_bin[td]) * ncell * 8;
+      if (USE_R && tid < 2 * NE - 1) reinterpret_cast<long*>(lds)[L::kOffA2 + tid] = (long)bin_of(t.anti_bin[ta]) * ncell * 8;
     }
     __syncthreads();
     if (live) {
@@ -393,9 +460,10 @@ collision_onepass_kernel(OnePassView w, const uint8_t* __restrict__ flags, long 
       for (int k = 1; k <= PF2 && k < NE; ++k) Pq[k % PF2] = __builtin_nontemporal_load(QP_PLANE_PTR(L::kOffD2 + k));
 #pragma unroll
       for (int k = 1; k < NE; ++k) {
-        const int entry = dbin[k];
         const double P = Pq[k % PF2];
         if (k + PF2 < NE) Pq[k % PF2] = __builtin_nontemporal_load(QP_PLANE_PTR(L::kOffD2 + k + PF2));
+        if (TRIM && k >= LMIN && k >= ne) continue;  // pad diagonals: no pair, no plane, no stash slot (the ring above stays unconditional)
+        const int entry = dbin[k];
         // G2 pairs at a time: their products first (independent instructions), then the sums - in the order of the
         // reference's bincount (ascending i): em - ab cancels to ~1e-5 of em near detailed balance, and (e^x - 1) / x
         // carries that amplification into the phonon planes; partial accumulators (another summation order) moved them
@@ -441,9 +509,10 @@ collision_onepass_kernel(OnePassView w, const uint8_t* __restrict__ flags, long 
       for (int m = 0; m < PF2 && m < 2 * NE - 1; ++m) Pq[m % PF2] = __builtin_nontemporal_load(QP_PLANE_PTR(L::kOffA2 + m));
 #pragma unroll
       for (int m = 0; m < 2 * NE - 1; ++m) {
-        const int entry = abin[m];
         const double P = Pq[m % PF2];
         if (m + PF2 < 2 * NE - 1) Pq[m % PF2] = __builtin_nontemporal_load(QP_PLANE_PTR(L::kOffA2 + m + PF2));
+        if (TRIM && m > AMIN && m > 2 * ne - 2) continue;
+        const int entry = abin[m];
         double rec = 0.0, pb = 0.0;
         // the pairs (i, j = m - i) with j <= i: i from ceil(m / 2) up to min(m, NE - 1)
         const int i_lo = (m + 1) / 2, i_hi = m < NE - 1 ? m : NE - 1;
@@ -502,6 +571,21 @@ static void launch_onepass(const OnePassView& v, const CollCall& c) {
   else
     hipLaunchKernelGGL((collision_onepass_kernel<NE, TB, S, R, false, PF, WAVES>), dim3(blocks), dim3(kOnePassThreads), 0,
                        c.stream, v, c.flags, c.ncell, c.sin, c.sout, c.ph, c.dE, c.dt);
+}
+// Padded bins: the kernel of the ceiling size NE with TRIM, the live size in OnePassView::ne_live
+typedef OnePassView view_onepasst;
+// (the ceiling's tiling; at NE = 50 with both processes the native kernel sits at exactly 256 registers and the guards' few
+// extra live values spilled 6 of them: its phase-2 prefetch ring is 10 deep instead of 12 - 253 registers, no scratch)
+template <int NE, bool S, bool R, int TB, int PF, int WAVES>
+static void launch_onepasst(const OnePassView& v, const CollCall& c) {
+  const unsigned blocks = (unsigned)((c.ncell + kOnePassThreads - 1) / kOnePassThreads);
+  constexpr int PF2 = (NE == 50 && S && R) ? 10 : 12;
+  if (c.u)
+    hipLaunchKernelGGL((collision_onepass_kernel<NE, TB, S, R, true, PF, WAVES, 7, 4, PF2, false, true>), dim3(blocks),
+                       dim3(kOnePassThreads), 0, c.stream, v, c.flags, c.ncell, c.sin, c.sout, c.ph, c.dE, c.dt);
+  else
+    hipLaunchKernelGGL((collision_onepass_kernel<NE, TB, S, R, false, PF, WAVES, 7, 4, 12, false, true>), dim3(blocks),
+                       dim3(kOnePassThreads), 0, c.stream, v, c.flags, c.ncell, c.sin, c.sout, c.ph, c.dE, c.dt);
 }
 // Gap-class form: one kernel per unit (each takes ~4 minutes to compile), so frozen (u0) and dynamic (u1) phonons are
 // families of their own and the dispatcher chooses between them.

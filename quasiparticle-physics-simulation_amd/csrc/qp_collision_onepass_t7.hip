@@ -1,0 +1,6 @@
+// One-pass collision kernel with trimmed bins (TRIM): ceiling NE = 32, scattering + recombination; tiling of the NE = 32 kernel.
+#include "qp_collision_onepass.inc"
+
+namespace qp {
+QP_DEFINE_LAUNCHER(32, onepasst, 1, 1, 16, 8, 2)
+}  // namespace qp

@@ -51,7 +51,8 @@ class GenerationProgram(_SizedStructure):
 
 # qp_collision_route_kind: what qp_collision_route returns for tables it accepts
 (ROUTE_ONEPASS, ROUTE_REGISTER, ROUTE_REGISTER_MEMBERS, ROUTE_ONEPASS_CLASSES, ROUTE_REGISTER_CLASSES, ROUTE_WAVE,
- ROUTE_GENERIC, ROUTE_COPY) = range(8)
+ ROUTE_GENERIC, ROUTE_COPY, ROUTE_ONEPASS_PADDED) = range(9)
+COLL_PAD_BINS = 16      # QP_COLL_PAD_BINS of qp_collision_tables.flags
 
 
 class RectPlan(C.Structure):
@@ -132,6 +133,7 @@ SIGNATURES = {
     "qp_collision_register_kernel_classes": (C.c_int, [C.c_int32]),
     "qp_collision_onepass_available": (C.c_int, [C.c_int32]),
     "qp_collision_member_tables_available": (C.c_int, [C.c_int32]),
+    "qp_collision_padded_ceiling": (C.c_int, [C.c_int32]),
     "qp_collision_pair_available": (C.c_int, [C.c_int32]),
     "qp_collision_route": (C.c_int, [C.POINTER(CollisionTables), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "qp_collision_double_step_guarded": (C.c_int, [C.POINTER(CollisionTables), c_dp, C.c_int64, c_dp, c_dp, c_dp, C.c_double,

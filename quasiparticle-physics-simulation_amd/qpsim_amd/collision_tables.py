@@ -118,7 +118,7 @@ class CollisionPlan:
 
 def plan_collision_tables(lib, ncell: int, mask_flat, kr0, ks0, rho, idx_diff, idx_sum, sign, cls_packed=None,
                           allow_fast=True, kernel: str = "auto", gap_params: dict | None = None, members: int = 1,
-                          member_classes: bool = False) -> CollisionPlan:
+                          member_classes: bool = False, pad_bins: bool = False) -> CollisionPlan:
     """Tables of ``Engine.make_collision_tables`` (which documents the arguments) for an engine of ``ncell`` cells with
     interior ``mask_flat``, on the host.  ``lib`` answers the ``qp_collision_*_available`` queries."""
     f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
@@ -190,17 +190,25 @@ def plan_collision_tables(lib, ncell: int, mask_flat, kr0, ks0, rho, idx_diff, i
     # member's cell count (the merged-bin stash is sized for it either way) ...
     members_ok = bool(member_classes and lib.qp_collision_member_tables_available(ne))
     # ... and at the one-pass sizes that kernel, whose 256-pixel blocks each stage the tables of one member
+    # (``pad_bins``: also at the sizes the one-pass kernel of a larger size serves, QP_COLL_PAD_BINS)
+    ceiling = int(lib.qp_collision_padded_ceiling(ne)) if pad_bins else 0
     members_onepass = bool(member_classes and kernel == "auto" and structure is not None and symmetric
-                           and ncell % 256 == 0 and lib.qp_collision_onepass_available(ne))
+                           and ncell % 256 == 0 and (lib.qp_collision_onepass_available(ne) or ceiling))
+    # padded bins: a size without a kernel of its own, one class or member classes; everything else plans as without it
+    padded = bool(ceiling and kernel == "auto" and structure is not None and symmetric
+                  and (members_onepass if member_classes else nclass == 1))
+    if padded:
+        flag_bits |= 16
     wave_ok = ne <= 64 and nw <= 192
     label = ("generic" if (kernel == "generic" or not wave_ok) else
-             "register" if (kernel == "auto" and structure is not None
-                            and ((members_ok or members_onepass) if member_classes else (nclass == 1 or classes_ok))
-                            and bool(lib.qp_collision_register_kernel_available(ne))) else "wave")
-    # 6. one-pass kernel (ne = 30, 32, 40, 50): the kernel tables once more in (anti)diagonal-major order (qpsim_hip.h);
-    # member classes: one image per member
+             "register" if padded or (kernel == "auto" and structure is not None
+                                      and ((members_ok or members_onepass) if member_classes
+                                           else (nclass == 1 or classes_ok))
+                                      and bool(lib.qp_collision_register_kernel_available(ne))) else "wave")
+    # 6. one-pass kernel (ne = 30, 32, 40, 50, or padded bins): the kernel tables once more in (anti)diagonal-major order
+    # (qpsim_hip.h), at the live size; member classes: one image per member
     if (label == "register" and (nclass == 1 or members_onepass) and symmetric
-            and bool(lib.qp_collision_onepass_available(ne))):
+            and (padded or bool(lib.qp_collision_onepass_available(ne)))):
         ksd, kra = onepass_tables(ks0, kr0, nclass, ne)
         arrays["ks0_diag"] = f64(ksd if nclass > 1 or ksd is None else ksd[0])
         arrays["kr0_anti2"] = f64(kra if nclass > 1 or kra is None else kra[0])

@@ -777,7 +777,7 @@ class Engine:
     # -- collisions, generation, reductions -------------------------------------------------------------------
     def make_collision_tables(self, kr0, ks0, rho, idx_diff, idx_sum, sign, cls_packed=None, allow_fast=True,
                               kernel: str = "auto", gap_params: dict | None = None, members: int = 1,
-                              member_classes: bool = False):
+                              member_classes: bool = False, pad_bins: bool = False):
         """Upload per-gap-class tables ([C,NE,NE], [C,NE]) and maps; returns an opaque handle.
 
         ``kernel``: "auto" | "generic" | "wave" | "wave_unstructured" forces a collision kernel (tests, A/B timing).
@@ -789,12 +789,16 @@ class Engine:
         is a multiple of 64, the one-pass kernel for NE = 30, 32, 40, 50 when it is a multiple of 256 (the handle then
         carries ``ks0_diag`` / ``kr0_anti2`` per member and reports ``kernel == "register"``); other shapes and sizes run
         the one-wave-per-pixel kernel through the class map.
+        ``pad_bins`` (opt-in, ``QP_COLL_PAD_BINS``): a size NE = 17 ... 49 without a kernel of its own
+        (``qp_collision_padded_ceiling(NE) != 0``) with structured symmetric maps and one class or member classes runs the
+        one-pass kernel of the next instantiated size on its live bins; every array keeps the live size.  Sizes with their
+        own kernel, NE >= 51 and gap classes plan exactly as without it.
 
         Every rule is ``collision_tables.plan_collision_tables`` (host only); this method uploads its arrays and fills the
         struct.  ``handle["kernel"]`` is the family the table set can reach (``collision_tables.CollisionPlan``)."""
         plan = collision_tables.plan_collision_tables(self.lib, self.ncell, self.mask_flat, kr0, ks0, rho, idx_diff, idx_sum,
                                                       sign, cls_packed, allow_fast, kernel, gap_params, members,
-                                                      member_classes)
+                                                      member_classes, pad_bins)
         h = {name: None if a is None else self.torch.as_tensor(a, device=self.device) for name, a in plan.arrays.items()}
         h.update(ne=plan.ne, nclass=plan.nclass, nw=plan.nw, merged_slots=plan.merged_slots, symmetric=plan.symmetric,
                  member_classes=plan.member_classes, kernel=plan.kernel, fast=plan.fast, pair=plan.pair,

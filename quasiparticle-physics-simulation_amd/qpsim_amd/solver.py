@@ -16,6 +16,13 @@ and only crosses PCIe at store points.  Additive keyword arguments (all optional
     instead of NumPy + an upload per step; its non-finite / negative check then arrives with the Pauli guard of the step
     (up to ``Engine.GUARD_LAG`` steps late, before anything is stored).  Expressions outside the subset, every other
     generation mode and the default ``False`` run exactly as before.
+``collision_padded_bins``
+    ``True`` lets a ``num_energy_bins`` between 17 and 49 that has no collision kernel of its own (every size but 18, 20,
+    24, 30, 32, 40) run the one-pass kernel of the next instantiated size (30, 32, 40, 50) on its live bins instead of the
+    one-wave-per-pixel kernel, where the phonon bin maps are structured and the gap is uniform (``QP_COLL_PAD_BINS``).
+    Sizes 51 ... 64, non-uniform gaps at any size and the double half-step pass (``num_energy_bins`` <= 16) are not
+    affected; the default ``False`` runs exactly as before.  Results agree with the default to rounding (another
+    summation order), not bit for bit.
 
 Table builders and helpers the reference exports from ``qpsim.solver`` are re-exported here under
 the same names.
@@ -337,11 +344,12 @@ def _initial_phonon_state(mask, omega_bins, bath_temperature, initial_condition_
 
 def _collision_tables(eng, E_bins, gap, nonuniform_pre, n, dynes_gamma, tau_r_eff, tau_s_eff, T_c, enable_recombination,
                       enable_scattering, idx_diff, idx_sum, diff_sign, members: int = 1, member_params=None,
-                      member_ids=None):
+                      member_ids=None, pad_bins: bool = False):
     """(device collision tables, rho per gap class) (solver.py:1189-1238); ``nonuniform_pre``: the precomputed arrays of a
     non-uniform gap (one class per distinct gap value), None for one gap.  ``member_params`` (ensemble parameter sweeps, one
     gap): ``(dynes_gamma, tau_r, tau_s, T_c)`` per member - one table set per member, each built exactly as that member's
-    lone run builds its own, uploaded as member classes; the rho returned is then [members, NE]."""
+    lone run builds its own, uploaded as member classes; the rho returned is then [members, NE].  ``pad_bins``
+    (``collision_padded_bins``) goes to the one-gap and the member-class tables; gap classes ignore it."""
     if member_params is not None:
         built: dict = {}
         for j, key in enumerate(member_params):
@@ -358,7 +366,7 @@ def _collision_tables(eng, E_bins, gap, nonuniform_pre, n, dynes_gamma, tau_r_ef
         kr_tab = np.stack([built[key][1] for key in member_params]) if enable_recombination else None
         ks_tab = np.stack([built[key][2] for key in member_params]) if enable_scattering else None
         ctab = eng.make_collision_tables(kr_tab, ks_tab, rho_tab, idx_diff, idx_sum, diff_sign, None,
-                                         members=len(member_params), member_classes=True)
+                                         members=len(member_params), member_classes=True, pad_bins=pad_bins)
         return ctab, rho_tab
     if nonuniform_pre is not None:
         gap_values = nonuniform_pre.get("gap_values")
@@ -373,7 +381,7 @@ def _collision_tables(eng, E_bins, gap, nonuniform_pre, n, dynes_gamma, tau_r_ef
               if enable_scattering else None)
     ctab = eng.make_collision_tables(kr_tab, ks_tab, rho_tab, idx_diff, idx_sum, diff_sign, cls,
                                      gap_params=dict(E=E_bins, gaps=class_gaps, tau_r=tau_r_eff, tau_s=tau_s_eff, T_c=T_c),
-                                     members=members)
+                                     members=members, pad_bins=bool(pad_bins and nonuniform_pre is None))
     return ctab, rho_tab
 
 
@@ -483,6 +491,7 @@ def run_2d_crank_nicolson(
     cn_rtol: float = 1e-13,
     device=None,
     generation_on_device: bool = False,
+    collision_padded_bins: bool = False,
 ):
     """Run the 2-D Crank-Nicolson diffusion (+ local collisions) time loop on the GPU.
 
@@ -526,7 +535,8 @@ def run_2d_crank_nicolson(
     omega_bins, idx_diff, idx_sum, diff_sign = _build_phonon_frequency_map(E_bins)
     phonon_host = _initial_phonon_state(mask, omega_bins, bath_temperature, initial_condition_spec)
     ctab, rho_tab = _collision_tables(eng, E_bins, gap, precomputed if nonuniform else None, n, dynes_gamma, tau_r_eff,
-                                      tau_s_eff, T_c, enable_recombination, enable_scattering, idx_diff, idx_sum, diff_sign)
+                                      tau_s_eff, T_c, enable_recombination, enable_scattering, idx_diff, idx_sum, diff_sign,
+                                      pad_bins=collision_padded_bins)
 
     state_host = _initial_qp_state(mask, initial_field, E_bins, dE, gap, dynes_gamma, energy_weights,
                                    initial_condition_spec)
