@@ -33,6 +33,7 @@
 #ifndef QPSIM_HIP_H
 #define QPSIM_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -395,6 +396,22 @@ int qp_collision_double_step_guarded_members(const qp_collision_tables* t, const
 
 /* out[p] = dE * sum_i state[i][p]  (energy integral of solver.py:1367,1480; sequential in i). */
 int qp_energy_integrate(const double* state, int32_t ne, int64_t ncell, double dE, double* out, void* stream);
+
+/*
+ * Region sums (time traces; no reference counterpart: the reference has `mass` at store points only).
+ * out[m][r][f] = sum of state[f][m][c] over the cells c of a member with bit r of region_bits[c] set, for nregion = 1 ... 8
+ * regions that may overlap; region_bits[ncell_member] is shared by all members and read INSTEAD of flags (clear the bits of
+ * cells outside the mask).  Every entry of out[members][nregion][nfield] is written; a region without cells gives 0.0.
+ * Two launches: blocks reduce fixed chunks of one (field, member) plane into the workspace (registers, wave shuffles,
+ * LDS), then one block per plane adds its chunk partials in index order.  The partition depends on the four sizes alone
+ * and there are no atomics and no completion counters, so equal inputs give bitwise equal outputs whatever else runs.
+ * 16-byte loads when `state` is 16-byte aligned (a plane that starts on an odd element takes one scalar cell first); any
+ * 8-byte aligned `state` gives the same bits.  Bandwidth-bound: 8 B per cell and field, 1 B per cell of bits.
+ * workspace: qp_region_sums_workspace_bytes(nfield, ncell_member, members, nregion) bytes (0 for sizes the call refuses).
+ */
+size_t qp_region_sums_workspace_bytes(int32_t nfield, int64_t ncell_member, int64_t members, int32_t nregion);
+int qp_region_sums(const double* state, const uint8_t* region_bits, int32_t nfield, int64_t ncell_member, int64_t members,
+                   int32_t nregion, void* workspace, double* out, void* stream);
 
 /* out[p] = sum_i state[i][p] * weights[i]  (phonon integrated occupation, solver.py:1358). */
 int qp_weighted_sum(const double* state, const double* weights, int32_t n, int64_t ncell, double* out, void* stream);

@@ -231,6 +231,106 @@ __global__ void __launch_bounds__(256) add_constant_members_kernel(const uint8_t
   }
 }
 
+// ---- region sums (time traces): out[m][r][f] = sum over the cells c of member m with bit r of bits[c] set of s[f][m][c] ----
+// Stage 1: block (chunk, m, f) reduces cells [chunk * kRegionChunk, ...) of plane (f, m) to `nregion` partials.  Stage 2:
+// block (m, f) adds the chunk partials of its plane in index order.  Which thread adds which cell, the shuffle tree, the
+// order of the four wave sums and the order of the chunks depend on the sizes alone, so a result is reproducible bit for
+// bit; nothing is accumulated across blocks in memory (no atomics, no completion counters).
+constexpr int kRegionChunk = 8192;   // cells of one plane per stage-1 block: 16 pairs per thread, two rounds of 8 loads
+constexpr int kRegionTile = 512;     // chunk partials (x nregion) that stage 2 holds in LDS per round
+
+// A plane starts at element (f * members + m) * ncm of `s`: with an odd ncm every second plane starts on an odd element.
+// The pairs of a chunk therefore start at its first EVEN element (one scalar head cell before them, at most one tail cell
+// after them): 16-byte loads when `s` itself is 16-byte aligned (VEC), else the same pairs from two 8-byte loads - the
+// additions and their order are the same either way.  NR = nregion rounded up to 1, 2, 4, 8.
+template <int NR, bool VEC>
+__global__ void __launch_bounds__(256) region_partial_kernel(const double* __restrict__ s, const uint8_t* __restrict__ bits,
+                                                             long ncm, long members, int nregion, long nchunk,
+                                                             double* __restrict__ part) {
+  const long chunk = blockIdx.x, m = blockIdx.y, f = blockIdx.z;
+  const long plane = f * members + m;
+  const long c0 = chunk * kRegionChunk;
+  const long left = ncm - c0;
+  const int n = (int)(left < kRegionChunk ? left : kRegionChunk);      // 1 ... kRegionChunk cells
+  const long e0 = plane * ncm + c0;
+  const int head = (int)(e0 & 1);                                       // n >= 1, so head <= n
+  const int npair = (n - head) >> 1;
+  const int tail = n - head - 2 * npair;
+  const double* p = s + e0 + head;
+  const uint8_t* b = bits + c0 + head;
+  double acc[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) acc[r] = 0.0;
+  auto add = [&](double v, unsigned bb) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] += ((bb >> r) & 1u) ? v : 0.0;
+  };
+  for (int i0 = threadIdx.x; i0 < npair; i0 += 8 * 256) {
+    double2 v[8];
+    unsigned bb[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int i = i0 + u * 256;
+      const bool in = i < npair;
+      if (VEC) v[u] = in ? reinterpret_cast<const double2*>(p)[i] : make_double2(0.0, 0.0);
+      else v[u] = in ? make_double2(p[2 * i], p[2 * i + 1]) : make_double2(0.0, 0.0);
+      bb[u] = in ? ((unsigned)b[2 * i] | ((unsigned)b[2 * i + 1] << 8)) : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      add(v[u].x, bb[u]);
+      add(v[u].y, bb[u] >> 8);
+    }
+  }
+  if (threadIdx.x == 0 && head) add(s[e0], bits[c0]);
+  if (threadIdx.x == 1 && tail) add(s[e0 + n - 1], bits[c0 + n - 1]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] += __shfl_down(acc[r], off, 64);
+  }
+  __shared__ double sm[4][NR];
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r) sm[threadIdx.x >> 6][r] = acc[r];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < nregion) {
+    const int r = threadIdx.x;
+    part[(plane * nchunk + chunk) * nregion + r] = ((sm[0][r] + sm[1][r]) + sm[2][r]) + sm[3][r];
+  }
+}
+
+__global__ void __launch_bounds__(64) region_final_kernel(const double* __restrict__ part, long nchunk, int nregion,
+                                                          long members, int nfield, double* __restrict__ out) {
+  __shared__ double tile[kRegionTile * 8];
+  const long m = blockIdx.x, f = blockIdx.y;
+  const double* src = part + (f * members + m) * nchunk * nregion;
+  double acc = 0.0;
+  for (long k0 = 0; k0 < nchunk; k0 += kRegionTile) {
+    const int nk = (int)(nchunk - k0 < kRegionTile ? nchunk - k0 : kRegionTile);
+    for (int t = threadIdx.x; t < nk * nregion; t += 64) tile[t] = src[k0 * nregion + t];
+    __syncthreads();
+    if ((int)threadIdx.x < nregion)
+      for (int k = 0; k < nk; ++k) acc += tile[k * nregion + threadIdx.x];
+    __syncthreads();
+  }
+  if ((int)threadIdx.x < nregion) out[(m * nregion + threadIdx.x) * nfield + f] = acc;
+}
+
+static inline long region_chunks(long ncm) { return (ncm + kRegionChunk - 1) / kRegionChunk; }
+
+template <int NR>
+static void region_partial_launch(bool vec, dim3 grid, hipStream_t stream, const double* s, const uint8_t* bits, long ncm,
+                                  long members, int nregion, long nchunk, double* part) {
+  if (vec)
+    hipLaunchKernelGGL((region_partial_kernel<NR, true>), grid, dim3(256), 0, stream, s, bits, ncm, members, nregion, nchunk,
+                       part);
+  else
+    hipLaunchKernelGGL((region_partial_kernel<NR, false>), grid, dim3(256), 0, stream, s, bits, ncm, members, nregion, nchunk,
+                       part);
+}
+
 __global__ void __launch_bounds__(256) absmax_partial_kernel(const double* __restrict__ a, long n, double* part) {
   double m = 0.0;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) {
@@ -416,6 +516,38 @@ int qp_energy_integrate(const double* state, int32_t ne, int64_t ncell, double d
   hipLaunchKernelGGL(qp::energy_integrate_kernel, dim3(qp::grid_for(ncell)), dim3(256), 0, (hipStream_t)stream, state,
                      (int)ne, (long)ncell, dE, out);
   return qp::check_launch("qp_energy_integrate");
+}
+
+size_t qp_region_sums_workspace_bytes(int32_t nfield, int64_t ncell_member, int64_t members, int32_t nregion) {
+  if (nfield < 1 || ncell_member < 1 || members < 1 || nregion < 1) return 0;
+  return (size_t)nfield * (size_t)members * (size_t)qp::region_chunks((long)ncell_member) * (size_t)nregion * sizeof(double);
+}
+
+int qp_region_sums(const double* state, const uint8_t* region_bits, int32_t nfield, int64_t ncell_member, int64_t members,
+                   int32_t nregion, void* workspace, double* out, void* stream) {
+  QP_REQUIRE(state && region_bits && workspace && out, "NULL argument");
+  QP_REQUIRE(nfield > 0 && ncell_member > 0 && members > 0, "nfield, ncell_member, members must be positive");
+  QP_REQUIRE(nregion >= 1 && nregion <= 8, "1 to 8 regions per call");
+  QP_REQUIRE(nfield <= 65535 && members <= 65535, "at most 65535 fields and 65535 members per call");
+  const long nchunk = qp::region_chunks((long)ncell_member);
+  QP_REQUIRE(nchunk <= 0x7fffffffL, "ncell_member too large for one launch");
+  const bool vec = ((unsigned long long)state & 15) == 0;
+  const dim3 grid((unsigned)nchunk, (unsigned)members, (unsigned)nfield);
+  auto* part = (double*)workspace;
+  const hipStream_t st = (hipStream_t)stream;
+  if (nregion == 1)
+    qp::region_partial_launch<1>(vec, grid, st, state, region_bits, (long)ncell_member, (long)members, 1, nchunk, part);
+  else if (nregion == 2)
+    qp::region_partial_launch<2>(vec, grid, st, state, region_bits, (long)ncell_member, (long)members, 2, nchunk, part);
+  else if (nregion <= 4)
+    qp::region_partial_launch<4>(vec, grid, st, state, region_bits, (long)ncell_member, (long)members, (int)nregion, nchunk,
+                                 part);
+  else
+    qp::region_partial_launch<8>(vec, grid, st, state, region_bits, (long)ncell_member, (long)members, (int)nregion, nchunk,
+                                 part);
+  hipLaunchKernelGGL(qp::region_final_kernel, dim3((unsigned)members, (unsigned)nfield), dim3(64), 0, st,
+                     (const double*)part, nchunk, (int)nregion, (long)members, (int)nfield, out);
+  return qp::check_launch("qp_region_sums");
 }
 
 int qp_weighted_sum(const double* state, const double* weights, int32_t n, int64_t ncell, double* out, void* stream) {

@@ -146,6 +146,26 @@ def compile_geometry(mask: np.ndarray, edges: list[EdgeSegment], edge_conditions
     return CompiledGeometry(mask, float(dx), flags, ex, ey, sx, sy)
 
 
+def pack_region_bits(regions, grid_mask: np.ndarray, offset=(0, 0)) -> np.ndarray:
+    """Up to 8 boolean regions given on a full frame -> one uint8 plane on the grid of ``grid_mask`` (the window of the full
+    frame at ``offset``: the solver crops padded geometries onto their bounding box).  Bit r of a cell is set when the cell
+    lies in region r AND inside the mask, so a kernel that reads the bits needs no flags.  Host only."""
+    grid_mask = np.asarray(grid_mask, dtype=bool)
+    regions = list(regions)
+    if not 1 <= len(regions) <= 8:
+        raise ValueError("1 to 8 regions fit into one plane of region bits")
+    ny, nx = grid_mask.shape
+    r0, c0 = int(offset[0]), int(offset[1])
+    bits = np.zeros((ny, nx), dtype=np.uint8)
+    for r, region in enumerate(regions):
+        region = np.asarray(region, dtype=bool)
+        window = region[r0:r0 + ny, c0:c0 + nx]
+        if region.ndim != 2 or window.shape != (ny, nx):
+            raise ValueError(f"region {r} of shape {region.shape} does not cover the {ny} x {nx} grid at offset ({r0}, {c0})")
+        bits |= (window & grid_mask).astype(np.uint8) << r
+    return bits
+
+
 # --------------------------------------------------------------------------------------------------------- #
 # device engine
 # --------------------------------------------------------------------------------------------------------- #
@@ -1091,6 +1111,23 @@ class Engine:
         _hip.check(self.lib.qp_energy_integrate(_ptr(state), state.numel() // nc, nc, float(dE), _ptr(out), self.stream),
                    "qp_energy_integrate")
         return out
+
+    def region_bits(self, regions, offset=(0, 0)):
+        """``pack_region_bits`` of up to 8 boolean full-frame regions on this engine's grid (the window of the full frame at
+        ``offset``), on the device as a uint8 plane [ncell]."""
+        return self.torch.as_tensor(pack_region_bits(regions, self.geom.mask, offset).reshape(-1), device=self.device)
+
+    def region_sums(self, state, bits, members: int, out_row) -> None:
+        """out_row[m][r][f] = sum over the cells of region r of state[f][m][cell] (``qp_region_sums``), ``state`` laid out
+        [field][member][cell] and ``out_row`` one [members, regions, fields] row of a caller-owned device buffer.  Enqueues
+        two kernels and nothing else: the sums stay on the device until the caller fetches its buffer."""
+        members, nregion, nfield = int(members), int(out_row.shape[-2]), int(out_row.shape[-1])
+        if state.numel() != nfield * members * self.ncell or not out_row.is_contiguous():
+            raise ValueError("region_sums: out_row must be a contiguous [members, regions, fields] row matching the state")
+        nbytes = int(self.lib.qp_region_sums_workspace_bytes(nfield, self.ncell, members, nregion))
+        ws = self.scratch("region_sums", (nbytes + 7) // 8)
+        _hip.check(self.lib.qp_region_sums(_ptr(state), _ptr(bits), nfield, self.ncell, members, nregion, _ptr(ws),
+                                           _ptr(out_row), self.stream), "qp_region_sums")
 
     def weighted_sum(self, planes, weights, ncell: int | None = None):
         """sum_k weights[k] planes[k]; ``weights`` on the host or already on the device, ``ncell`` as ``energy_integral``."""

@@ -19,6 +19,11 @@ Rounding: members are bit-equal to their lone ``run_2d_crank_nicolson`` call wit
 the same ADI tile family (``QPSIM_FINE_TILES``) and the same step form (``QPSIM_ADI_FUSED``: a batch of at least 4 Mi
 cells takes the one-pass steps, which round the interface rows differently, while a smaller lone member does not), within
 2e-13 relative otherwise, and within 1e-12 relative with ``cn_exact`` (the iteration's stop test is global over the batch).
+
+Time traces (``trace_out=[]`` of the ensemble call, ``trace_regions`` / ``trace_every`` in the common arguments): one
+reduction launch per sample serves all members of a batch.  A member's trace is bit-equal to its lone run's where its state
+is (the conditions above) and the device grid holds an even number of cells; with an odd count every second member plane
+starts on an odd element, pairs its cells differently, and the sums agree to rounding.
 """
 from __future__ import annotations
 
@@ -128,18 +133,24 @@ def generation_amounts(specs, t_start: float, dt_of_step: float) -> list:
     return [S._generation_amount(spec, t_start, dt_of_step) for spec in specs]
 
 
-def _bytes_per_member(kw: dict) -> float:
-    """Device bytes one member needs: state planes (x2), phonon planes, diffusion / exact-CN work planes."""
+def _bytes_per_member(kw: dict, traced: bool = False) -> float:
+    """Device bytes one member needs: state planes (x2), phonon planes, diffusion / exact-CN work planes and, when time
+    traces are taken (``traced``), its share of the trace buffer."""
     mask = np.asarray(kw["mask"], dtype=bool)
     rows, cols = np.flatnonzero(mask.any(axis=1)), np.flatnonzero(mask.any(axis=0))
     ncell = (rows[-1] - rows[0] + 1) * (cols[-1] - cols[0] + 1) if rows.size else 1
     ne = int(kw["num_energy_bins"]) if kw["energy_gap"] > 0.0 else 1
     nw = 3 * ne
-    return 8.0 * ncell * (8 * ne + 3 * nw + 8)
+    trace = 0.0
+    if traced:
+        regions = 1 if kw["trace_regions"] is None else len(kw["trace_regions"])
+        trace = 8.0 * Schedule(kw["total_time"], kw["dt"], 1, kw["trace_every"]).samples * regions * ne
+    return 8.0 * ncell * (8 * ne + 3 * nw + 8) + trace
 
 
 def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = None, errors: str = "raise",
-                                   max_members_per_batch: int | None = None, process_group=None, **common) -> list:
+                                   max_members_per_batch: int | None = None, process_group=None,
+                                   trace_out: list | None = None, **common) -> list:
     """Run ``len(members)`` independent problems batched on the device.
 
     ``common`` takes the keyword arguments of ``run_2d_crank_nicolson``; ``members[m]`` overrides only the keys of
@@ -155,10 +166,20 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
     ``errors="raise"`` the first violation (earliest step, then lowest member) raises ``ValueError("member m: ...")``.
     Members run in consecutive batches when they do not all fit on the device (``max_members_per_batch`` caps a batch).
     With an initialised ``process_group`` of world size > 1, rank r runs ``shard_members(M, world, r)`` on its current
-    device and every rank returns the full list."""
+    device and every rank returns the full list.
+    Time traces: ``trace_regions`` / ``trace_every`` are shared keys of ``common``; the sink is the list ``trace_out`` of
+    THIS call (never a member key), cleared at entry and filled on normal return with one dict per member as the lone
+    call fills its ``trace_out`` (None for a member that failed under ``errors="return"``).  One reduction launch per sample
+    serves all members of a batch."""
     if errors not in ("raise", "return"):
         raise ValueError("errors must be 'raise' or 'return'")
     kws = member_arguments(list(members), common, sweep)
+    traces: dict | None = None if trace_out is None else {}
+    if trace_out is not None:
+        trace_out.clear()
+    if kws:                        # refuse bad trace arguments before any device is touched
+        S._trace_plan(np.asarray(kws[0]["mask"], dtype=bool), traces is not None, kws[0]["trace_regions"],
+                      kws[0]["trace_every"])
     _STATS.clear()
     _STATS.update(batches=0, pair_passes=0, guarded_calls=0)
     device_expr.reset_run_stats()
@@ -177,22 +198,25 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
         dev = kws[0].get("device")
         dev = torch.device("cuda", torch.cuda.current_device()) if (dev is None or world > 1) else torch.device(dev)
         free = float(torch.cuda.mem_get_info(dev)[0])
-    batches = plan_batches(mine, _bytes_per_member(kws[0]), free, max_members_per_batch)
+    batches = plan_batches(mine, _bytes_per_member(kws[0], traces is not None), free, max_members_per_batch)
     # one batch on one process raises at once; otherwise every batch finishes and the earliest violation is raised after
     eager = errors == "raise" and world == 1 and len(batches) == 1
     results: dict[int, object] = {}
     for batch in batches:
-        res = _run_batch([kws[m] for m in batch], batch, "raise" if eager else "return", None if world == 1 else dev)
+        res = _run_batch([kws[m] for m in batch], batch, "raise" if eager else "return", None if world == 1 else dev,
+                         traces)
         results.update(zip(batch, res))
     out = [results.get(m) for m in range(len(kws))]
     if world > 1:
         import torch.distributed as dist
-        local = [(m, results[m], kws[m]["phonon_history_out"]) for m in mine]
+        local = [(m, results[m], kws[m]["phonon_history_out"], None if traces is None else traces.get(m)) for m in mine]
         gathered = [None] * world
         dist.all_gather_object(gathered, local, group=process_group)
         for part in gathered:
-            for m, res, ph in part:
+            for m, res, ph, tr in part:
                 out[m] = res
+                if traces is not None:
+                    traces[m] = tr
                 target = kws[m]["phonon_history_out"]
                 if target is not None and ph is not None and target is not ph:
                     target.clear()
@@ -201,16 +225,18 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
         failures = [(getattr(r, "step", 0), m, r) for m, r in enumerate(out) if isinstance(r, Exception)]
         if failures:
             raise min(failures, key=lambda f: f[:2])[2]
+    if trace_out is not None:
+        trace_out.extend(traces.get(m) for m in range(len(kws)))
     return out
 
 
-def _run_batch(kws: list[dict], ids: list[int], errors: str, device=None) -> list:
+def _run_batch(kws: list[dict], ids: list[int], errors: str, device=None, traces: dict | None = None) -> list:
     import torch
     dev = kws[0]["device"] if device is None else device
     dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
     with torch.cuda.device(dev):
         _STATS["batches"] += 1
-        return _run_batch_on_device(kws, ids, errors, dev)
+        return _run_batch_on_device(kws, ids, errors, dev, traces)
 
 
 def _prefixed(m: int, fn, *args):
@@ -220,7 +246,9 @@ def _prefixed(m: int, fn, *args):
         raise type(exc)(f"member {m}: {exc}") from exc
 
 
-def _run_batch_on_device(kws, ids, errors, device):
+def _run_batch_on_device(kws, ids, errors, device, traces=None):
+    """One batch; ``traces`` ({member id: trace dict}, None without time traces) receives what each member's ``trace_out``
+    would."""
     a = kws[0]
     checked = [_prefixed(ids[j], S._checked_run_arguments, k["mask"], k["initial_field"], k["diffusion_coefficient"],
                          k["dt"], k["total_time"], k["store_every"], k["enable_diffusion"], k["enable_recombination"],
@@ -229,16 +257,31 @@ def _run_batch_on_device(kws, ids, errors, device):
     mask, _, store_every, n, _, _ = checked[0]
     inits = [c[1] for c in checked]
     geom = S._run_geometry(mask, a["edges"], a["edge_conditions"], a["dx"], a["enable_diffusion"])
-    sched = Schedule(a["total_time"], a["dt"], store_every)
+    trace = S._trace_plan(mask, traces is not None, a["trace_regions"], a["trace_every"])
+    sched = Schedule(a["total_time"], a["dt"], store_every, None if trace is None else trace.every)
+    energy = a["energy_gap"] > 0.0
+    nplanes = a["num_energy_bins"] if energy else 1
+    S._check_trace_buffer(trace, sched, len(kws), nplanes)
     eng = Engine(geom, device=device)
     eng.pin_stream()
     flags = eng.d_flags.reshape(-1).repeat(len(kws))     # [member][cell]
     out = Outputs(mask, a["dx"], [k["progress_callback"] for k in kws])
-    if not a["energy_gap"] > 0.0:
-        return S._run_scalar(eng, sched, out, inits, [k["diffusion_coefficient"] for k in kws], a["enable_diffusion"],
-                             [k["bath_temperature"] for k in kws], [k["phonon_history_out"] for k in kws],
-                             a["diffusion_scheme"], a["cn_rtol"])
-    return _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, [(c[4], c[5]) for c in checked])
+    tracer = S._tracer(eng, mask, trace, sched, len(kws), nplanes)
+    if not energy:
+        results = S._run_scalar(eng, sched, out, inits, [k["diffusion_coefficient"] for k in kws], a["enable_diffusion"],
+                                [k["bath_temperature"] for k in kws], [k["phonon_history_out"] for k in kws],
+                                a["diffusion_scheme"], a["cn_rtol"], tracer)
+    else:
+        results = _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, [(c[4], c[5]) for c in checked],
+                                    tracer)
+    if tracer is not None:
+        E_bins, dE = (S.build_energy_grid(a["energy_gap"], a["energy_min_factor"], a["energy_max_factor"], nplanes)
+                      if energy else (None, None))
+        density = tracer.density()
+        for j, res in enumerate(results):
+            traces[ids[j]] = None if isinstance(res, Exception) else S._trace_result(trace, tracer.times, density[:, j],
+                                                                                     E_bins, a["dx"], dE)
+    return results
 
 
 def table_parameters(kws: list[dict], taus: list[tuple]) -> list[tuple]:
@@ -344,7 +387,7 @@ class _MembersRun(EnergyRun):
                 warnings.warn(f"member {self.ids[m]}: {warning}", stacklevel=8)
 
 
-def _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, taus):
+def _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, taus, tracer=None):
     """Energy-resolved mode for M members: the setup of ``run_2d_crank_nicolson`` over [bin][member][cell] planes."""
     a, M, mask = kws[0], len(kws), out.mask
     tau_s_eff, tau_r_eff = taus[0]
@@ -383,7 +426,7 @@ def _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, taus):
     run.ctab, run.floor, run.physics = ctab, a["pauli_density_floor"], (en_r, en_s, not a["freeze_phonon_dynamics"])
     run.flags, run.generations = flags, [
         S._Generation(k["external_generation"], mask, E_bins, on_device=a["generation_on_device"]) for k in kws]
-    run.ids, run.errors = ids, errors
+    run.ids, run.errors, run.tracer = ids, errors, tracer
     run.verdict = S._guard_rule(eng, mask, E_bins, a["enforce_pauli"], a["pauli_warn_threshold"], a["pauli_error_threshold"])
     run.quiet_below = min([v for v in (a["pauli_warn_threshold"], a["pauli_error_threshold"]) if v is not None],
                           default=float("inf"))

@@ -23,6 +23,16 @@ and only crosses PCIe at store points.  Additive keyword arguments (all optional
     Sizes 51 ... 64, non-uniform gaps at any size and the double half-step pass (``num_energy_bins`` <= 16) are not
     affected; the default ``False`` runs exactly as before.  Results agree with the default to rounding (another
     summation order), not bit for bit.
+``trace_out``, ``trace_regions``, ``trace_every``
+    Time traces without stored frames: with a dict as ``trace_out`` the sums of every energy plane over up to 8 named
+    regions (``trace_regions``: name -> boolean array of the mask's shape, regions may overlap; None: one region ``"all"``
+    = the mask) are reduced on the device at t = 0, every ``trace_every``-th step and the last step, kept there, and
+    fetched once when the run ends.  ``trace_out`` is cleared at entry and filled on normal return with ``times`` [S],
+    ``regions`` (names), ``cells`` (interior cells per region), ``energy_bins`` (None in scalar mode), ``density``
+    [S, R, NE] = sum over the region's cells of each plane (scalar mode: NE = 1, the plane is u) and ``number`` [S, R] =
+    dx^2 dE sum_i density (scalar mode: dx^2 density).  A sampled step is sequenced like a stored one (no fused pair pass
+    across it), so its state is bit for bit the state a run with ``store_every = trace_every`` stores there.  The default
+    ``trace_out=None`` runs exactly as before.
 
 Table builders and helpers the reference exports from ``qpsim.solver`` are re-exported here under
 the same names.
@@ -46,7 +56,7 @@ from .models import (
 )
 from . import device_expr
 from .safe_eval import compile_safe_expression
-from .timeloop import EnergyRun, Outputs, Schedule, energy_loop, scalar_loop
+from .timeloop import EnergyRun, Outputs, Schedule, Tracer, energy_loop, scalar_loop
 
 # names the reference exposes from qpsim.solver
 build_energy_grid = _tb.build_energy_grid
@@ -284,6 +294,67 @@ def _checked_run_arguments(mask, initial_field, diffusion_coefficient, dt, total
     return mask, initial_field, store_every, n, tau_s_eff, tau_r_eff
 
 
+TRACE_BUFFER_LIMIT = 256 << 20      # bytes of the device buffer of a time trace (samples x members x regions x planes x 8)
+
+
+class _TracePlan:
+    """Checked time-trace arguments of a run: region ``names``, their boolean arrays on the full mask (``regions``), the
+    interior ``cells`` of each and ``every``."""
+
+    def __init__(self, names, regions, cells, every):
+        self.names, self.regions, self.cells, self.every = names, regions, cells, every
+
+
+def _trace_plan(mask: np.ndarray, tracing: bool, trace_regions, trace_every):
+    """The ``_TracePlan`` of a run, None when traces are off (``tracing``: a sink was given).  ``ValueError`` naming the
+    argument for ``trace_every`` < 1, regions without a sink, not 1 ... 8 regions, a region of another shape than the mask."""
+    if isinstance(trace_every, bool) or not isinstance(trace_every, (int, np.integer)) or trace_every < 1:
+        raise ValueError(f"trace_every must be an integer >= 1, got {trace_every!r}.")
+    if not tracing:
+        if trace_regions is not None:
+            raise ValueError("trace_regions needs trace_out: without a sink no trace is taken.")
+        return None
+    if trace_regions is None:
+        trace_regions = {"all": mask}
+    if not isinstance(trace_regions, dict) or not 1 <= len(trace_regions) <= 8:
+        raise ValueError("trace_regions must map 1 to 8 region names to boolean arrays"
+                         + (f", got {len(trace_regions)} regions." if isinstance(trace_regions, dict) else "."))
+    names, regions = [], []
+    for name, region in trace_regions.items():
+        region = np.asarray(region)
+        if region.shape != mask.shape:
+            raise ValueError(f"trace_regions['{name}'] has shape {region.shape}; expected the mask's shape {mask.shape}.")
+        names.append(str(name))
+        regions.append(region.astype(bool))
+    return _TracePlan(names, regions, [int(np.sum(r & mask)) for r in regions], int(trace_every))
+
+
+def _check_trace_buffer(plan, sched: Schedule, members: int, nfield: int) -> None:
+    if plan is None:
+        return
+    nbytes = 8 * sched.samples * members * len(plan.names) * nfield
+    if nbytes > TRACE_BUFFER_LIMIT:
+        raise ValueError(f"trace_every={plan.every} gives a trace buffer of {nbytes / 2 ** 20:.0f} MiB ({sched.samples} samples x "
+                         f"{members} members x {len(plan.names)} regions x {nfield} planes x 8 B), above the limit of "
+                         f"{TRACE_BUFFER_LIMIT >> 20} MiB; use a larger trace_every.")
+
+
+def _tracer(eng, mask, plan, sched: Schedule, members: int, nfield: int):
+    """The ``Tracer`` of a run on ``eng`` (whose grid is the bounding box of ``mask``), None without a plan."""
+    if plan is None:
+        return None
+    offset = (int(np.flatnonzero(mask.any(axis=1))[0]), int(np.flatnonzero(mask.any(axis=0))[0]))
+    return Tracer(eng, eng.region_bits(plan.regions, offset), len(plan.names), members, nfield, sched.samples)
+
+
+def _trace_result(plan, times, density: np.ndarray, E_bins, dx: float, dE) -> dict:
+    """What ``trace_out`` receives for one problem; ``density`` [S, R, planes] of that problem."""
+    density = np.ascontiguousarray(density)
+    number = dx * dx * (density[..., 0] if E_bins is None else dE * np.sum(density, axis=-1))
+    return {"times": list(times), "regions": list(plan.names), "cells": list(plan.cells),
+            "energy_bins": None if E_bins is None else np.array(E_bins, dtype=float), "density": density, "number": number}
+
+
 def _run_geometry(mask, edges, edge_conditions, dx, enable_diffusion):
     """Compiled geometry of the device grid = bounding box of the mask."""
     dev_mask, dev_edges = _crop_to_bounding_box(mask, edges)
@@ -492,15 +563,22 @@ def run_2d_crank_nicolson(
     device=None,
     generation_on_device: bool = False,
     collision_padded_bins: bool = False,
+    trace_out: dict[str, Any] | None = None,
+    trace_regions: dict[str, np.ndarray] | None = None,
+    trace_every: int = 1,
 ):
     """Run the 2-D Crank-Nicolson diffusion (+ local collisions) time loop on the GPU.
 
     Returns ``(times, frames, mass, color_limits, energy_frames_or_None, energy_bins_or_None)`` exactly
-    as the reference does; ``phonon_history_out`` is cleared and filled the same way.
+    as the reference does; ``phonon_history_out`` is cleared and filled the same way, and so is ``trace_out`` (module
+    docstring) when time traces are wanted.
     """
     mask, initial_field, store_every, n, tau_s_eff, tau_r_eff = _checked_run_arguments(
         mask, initial_field, diffusion_coefficient, dt, total_time, store_every, enable_diffusion, enable_recombination,
         enable_scattering, tau_0, tau_s, tau_r, external_generation, phonon_history_out)
+    trace = _trace_plan(mask, trace_out is not None, trace_regions, trace_every)
+    if trace_out is not None:
+        trace_out.clear()
     device_expr.reset_run_stats()
 
     # Device grid = bounding box of the mask.  Interior cells keep their argwhere (row-major) order under the crop, so
@@ -508,14 +586,20 @@ def run_2d_crank_nicolson(
     # mask whose interior is a solid rectangle inside a padded frame (the reference's built-in geometry) thereby
     # becomes a full rectangle on the device and takes the tiled ADI path.
     geom = _run_geometry(mask, edges, edge_conditions, dx, enable_diffusion)
-    sched = Schedule(total_time, dt, store_every)
+    sched = Schedule(total_time, dt, store_every, None if trace is None else trace.every)
+    nplanes = num_energy_bins if energy_gap > 0.0 else 1
+    _check_trace_buffer(trace, sched, 1, nplanes)
     eng = Engine(geom, device=device)
     eng.pin_stream()          # one stream for the whole run: skip the per-launch lookup
     out = Outputs(mask, dx, [progress_callback])
+    tracer = _tracer(eng, mask, trace, sched, 1, nplanes)
 
     if not energy_gap > 0.0:
-        return _run_scalar(eng, sched, out, [initial_field], [diffusion_coefficient], enable_diffusion, [bath_temperature],
-                           [phonon_history_out], diffusion_scheme, cn_rtol)[0]
+        result = _run_scalar(eng, sched, out, [initial_field], [diffusion_coefficient], enable_diffusion, [bath_temperature],
+                             [phonon_history_out], diffusion_scheme, cn_rtol, tracer)[0]
+        if tracer is not None:
+            trace_out.update(_trace_result(trace, tracer.times, tracer.density()[:, 0], None, dx, None))
+        return result
 
     # ------------------------------------------------------------------ energy-resolved mode
     gap = energy_gap
@@ -547,6 +631,7 @@ def run_2d_crank_nicolson(
     run.physics = (enable_recombination, enable_scattering, not freeze_phonon_dynamics)
     run.generation = _Generation(external_generation, mask, E_bins, on_device=generation_on_device)
     run.verdict = _guard_rule(eng, mask, E_bins, enforce_pauli, pauli_warn_threshold, pauli_error_threshold)
+    run.tracer = tracer
 
     collisions = bool(enable_recombination or enable_scattering)
     energy_loop(run, sched, diffuser, collisions=collisions,
@@ -558,6 +643,8 @@ def run_2d_crank_nicolson(
     if phonon_history_out is not None:
         phonon_history_out.clear()
         phonon_history_out.update(_dynamic_phonon_history(out, 0, omega_bins))
+    if tracer is not None:
+        trace_out.update(_trace_result(trace, tracer.times, tracer.density()[:, 0], E_bins, dx, dE))
     return out.times, out.frames[0], out.mass[0], _color_limits(out.frames[0]), out.energy_frames[0], E_bins
 
 
@@ -720,9 +807,9 @@ def _dynamic_phonon_history(out: Outputs, m: int, omega_bins) -> dict:
 
 
 def _run_scalar(eng: Engine, sched, out: Outputs, inits, coefficients, enable_diffusion, bath_temperatures, histories,
-                scheme, rtol) -> list:
+                scheme, rtol, tracer=None) -> list:
     """Legacy scalar mode, energy_gap == 0 (solver.py:1517-1587), for M members as one [M, ncell] field set; the result
-    tuple of every member."""
+    tuple of every member.  ``tracer``: the time traces of the M fields (one plane per member), read by the caller."""
     mask, M = out.mask, out.members
     u_host = np.stack([f[mask].astype(float) for f in inits])
     u = eng.upload_packed(u_host)
@@ -730,7 +817,7 @@ def _run_scalar(eng: Engine, sched, out: Outputs, inits, coefficients, enable_di
                 if enable_diffusion else None)
     out.add_host_frames(0.0, [reconstruct_field(mask, v) for v in u_host],
                         [float(np.sum(v) * out.dx * out.dx) for v in u_host])
-    scalar_loop(sched, diffuser, u, out, eng)
+    scalar_loop(sched, diffuser, u, out, eng, tracer)
     for T_bath, history in zip(bath_temperatures, histories):
         if history is not None:
             f, ef, bins, meta = build_fixed_phonon_history(mask=mask, times=out.times, bath_temperature=T_bath,

@@ -7,6 +7,12 @@ and opening half-step, the Pauli guard read ``guard_lag`` steps late, the short 
 [bin][member][cell], the ``*_members`` calls) both derive from ``EnergyRun``, which holds what they share: the device planes,
 the ``state`` / ``state_alt`` swap and the store point.  ``Outputs`` keeps the host-side results of M members; a lone run is
 M = 1.
+
+Time traces (opt-in): a ``Schedule`` with ``trace_every`` also names *sampled* steps, and a ``Tracer`` enqueues at each of
+them the region sums of every plane of the state into one row of a device buffer that is fetched once, after the loop.  A
+sampled step is sequenced exactly like a stored one (no pair pass across it, the stretch of diffusion steps ends there, the
+guard is read), so the state it sees is the state a run with ``store_every = trace_every`` stores there; it downloads no
+frame.  Without a tracer no step is sampled and both loops issue exactly the calls they issued before.
 """
 from __future__ import annotations
 
@@ -23,14 +29,25 @@ def _step_plan(total_time: float, dt: float) -> tuple[int, float, int]:
 
 
 class Schedule:
-    """Step sizes and store points of a run: ``full_steps`` steps of ``dt``, then one of ``rem`` if that is positive."""
+    """Step sizes and store points of a run: ``full_steps`` steps of ``dt``, then one of ``rem`` if that is positive.
+    ``trace_every`` (None: no traces) adds the sampled steps of a time trace: every ``trace_every``-th and the last."""
 
-    def __init__(self, total_time: float, dt: float, store_every: int):
-        self.dt, self.store_every = dt, store_every
+    def __init__(self, total_time: float, dt: float, store_every: int, trace_every: int | None = None):
+        self.dt, self.store_every, self.trace_every = dt, store_every, trace_every
         self.full_steps, self.rem, self.total_steps = _step_plan(total_time, dt)
 
     def stored(self, step: int) -> bool:
         return step % self.store_every == 0 or step == self.total_steps
+
+    def sampled(self, step: int) -> bool:
+        return self.trace_every is not None and (step % self.trace_every == 0 or step == self.total_steps)
+
+    @property
+    def samples(self) -> int:
+        """Rows of a trace: t = 0 and every sampled step."""
+        if self.trace_every is None:
+            return 0
+        return 1 + self.total_steps // self.trace_every + (1 if self.total_steps % self.trace_every else 0)
 
     def dt_of(self, step: int) -> float:
         return self.rem if step > self.full_steps else self.dt
@@ -131,19 +148,45 @@ class Outputs:
         self.lazy.add(ticket, lambda arr: [series[m].__setitem__(k, arr[m]) for m in range(self.members)])
 
 
-def scalar_loop(sched: Schedule, diffuser, u, out: Outputs, eng) -> None:
-    """Legacy scalar mode, energy_gap == 0 (solver.py:1540-1555): nothing happens between two store points but diffusion
-    steps, which ``diffuser.advance`` takes in one go."""
+class Tracer:
+    """Time traces of M members: at every sample the sums of each plane [field][member][cell] over up to 8 regions
+    (``Engine.region_sums``) go into row k of a device buffer [samples, M, regions, fields]; nothing is read back before
+    ``density()``.  ``bits`` is the device plane of ``Engine.region_bits``."""
+
+    def __init__(self, eng, bits, nregion: int, members: int, nfield: int, samples: int):
+        self.eng, self.bits, self.members = eng, bits, members
+        self.buffer = eng.empty(samples, members, nregion, nfield)
+        self.times: list[float] = []
+
+    def sample(self, t: float, state) -> None:
+        self.eng.region_sums(state, self.bits, self.members, self.buffer[len(self.times)])
+        self.times.append(float(t))
+
+    def density(self) -> np.ndarray:
+        """[samples taken, M, regions, fields] on the host (the one transfer of a trace)."""
+        return self.buffer[:len(self.times)].cpu().numpy()
+
+
+def scalar_loop(sched: Schedule, diffuser, u, out: Outputs, eng, tracer: Tracer | None = None) -> None:
+    """Legacy scalar mode, energy_gap == 0 (solver.py:1540-1555): nothing happens between two store points (or sampled
+    steps of ``tracer``) but diffusion steps, which ``diffuser.advance`` takes in one go."""
     t = 0.0
     done = 0
+    if tracer is not None:
+        tracer.sample(0.0, u)
     for step in range(1, sched.total_steps + 1):
         t += sched.dt_of(step)                        # same accumulation order as the reference
-        if sched.stored(step):
+        stored = sched.stored(step)
+        sampled = tracer is not None and sched.sampled(step)
+        if stored or sampled:
             if diffuser is not None:
                 diffuser.advance(u, done + 1, step, sched.full_steps)
             done = step
+        if stored:
             out.times.append(float(t))
             out.add_integrated(t, _device_frames_async(eng, u, out.mask))
+        if sampled:
+            tracer.sample(t, u)
     out.lazy.flush()
 
 
@@ -157,7 +200,10 @@ class EnergyRun:
     ``collide_pair(dt_a, dt_b, amount)``               the fused closing + opening half-step; the guard ticket
     ``guard_launch()``                                 the guard of ``state`` on its own; its ticket
     ``guard_check(ticket, step, t)``                   reads a ticket; warns / raises with the step and time it belongs to
+
+    ``tracer``: the ``Tracer`` of the run, None (the default) without time traces.
     """
+    tracer: Tracer | None = None
 
     def __init__(self, eng, out: Outputs, state, state_alt, phonon, dE: float, phonon_widths=None):
         self.eng, self.out = eng, out
@@ -194,8 +240,11 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
     ``batch_diffusion``: pure diffusion with a guard that cannot fire - the steps between two store points are one call.
     ``pair_ok``: Strang steps that follow one another without a store point in between run the closing half-step of step k
     and the opening half-step of step k + 1 as ONE pass over the state (``run.collide_pair``); ``opened`` says that the
-    generation term and the first half-step of the step now starting were already applied by that pass."""
+    generation term and the first half-step of the step now starting were already applied by that pass.
+    A sampled step of ``run.tracer`` ends a stretch exactly as a stored one does (``halt``) and enqueues the region sums of
+    the state instead of a download."""
     pending: list = []
+    tracer = run.tracer
 
     def guard_flush(keep: int = 0) -> None:
         while len(pending) > keep:
@@ -215,6 +264,8 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
     pending.append((run.guard_launch(), 0, 0.0))
     guard_flush()
     run.store(0.0)
+    if tracer is not None:
+        tracer.sample(0.0, run.state)
     times = run.out.times
     t = 0.0
     done = 0
@@ -223,13 +274,18 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
         final = step > sched.full_steps
         dt_step = sched.dt_of(step)
         stored = sched.stored(step)
+        sampled = tracer is not None and sched.sampled(step)
+        halt = stored or sampled
         if batch_diffusion:
             t += dt_step
-            if stored:
+            if halt:
                 diffuser.advance(run.state, done + 1, step, sched.full_steps)
                 done = step
+            if stored:
                 times.append(float(t))
                 run.store(t)
+            if sampled:
+                tracer.sample(t, run.state)
             continue
         if not opened:
             run.generate(t, dt_step)
@@ -239,7 +295,7 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
             opened = False
             diffuser.step(run.state, final)
             amount = None
-            if pair_ok and step < sched.total_steps and not stored and dt_step > 0.0:
+            if pair_ok and step < sched.total_steps and not halt and dt_step > 0.0:
                 dt_next = sched.dt_of(step + 1)
                 amount = run.pair_amount(t + dt_step, dt_next)
             if amount is not None:
@@ -255,10 +311,12 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
                 diffuser.step(run.state, final)
         if not guarded:
             pending.append((run.guard_launch(), step, t + dt_step))
-        guard_flush(keep=0 if stored else guard_lag)
+        guard_flush(keep=0 if halt else guard_lag)
         t += dt_step
         if stored:
             times.append(float(t))
             run.store(t)
+        if sampled:
+            tracer.sample(t, run.state)
     guard_flush()
     run.out.lazy.flush()
