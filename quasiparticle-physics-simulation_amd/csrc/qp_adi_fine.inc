@@ -116,6 +116,7 @@ __device__ __forceinline__ void ends32_pair(const double (&e)[FS], const FineVie
 constexpr int QB = 16;
 constexpr int QP = QB + 1;
 constexpr int FINE_LDS_DOUBLES = 4 * QB * QP;
+constexpr int FINE_LDS_PAIRS = 2 * 64;      // one (first, last) pair per lane of the one-pass kernel (fine_p_map)
 
 __device__ __forceinline__ void swap_lane_rows(double& lo_reg, double& hi_reg) {
   // odd 16-lane rows of lo_reg <-> even 16-lane rows of hi_reg
@@ -343,13 +344,13 @@ __device__ __forceinline__ double fine_col_source(const FineView& vn, double an,
 }
 
 // Middle of a y-pass on one y-chunk per lane (lane = column, register = row), shared by fine_y_body and
-// fine_fused_kernel; the ghosts gu / gd are finished.  MODE 1 / 2: the y-solve; MODE 2 stores the solution and stops.
+// fine_fused_kernel; the ghosts gu / gd are finished.  `before_store` runs between the last arithmetic and the stores.  MODE 1 / 2: the y-solve; MODE 2 stores the solution and stops.
 // MODE 0 / 1: the explicit y-operator (table cyn, weight an, column source scol), the source plane (SRC: bscale * bt),
 // and the store.  MODE 3 does nothing here.
-template <int MODE, int STREAM, bool SRC, class CoefY, class CoefYN>
+template <int MODE, int STREAM, bool SRC, class CoefY, class CoefYN, class Hook = FineNoHook>
 __device__ __forceinline__ void fine_y_mid(double (&e)[FS], double gu, double gd, double a, const CoefY& cy, double an,
                                            const CoefYN& cyn, double scol, double bscale, const double* bt, double* dp,
-                                           long pitch) {
+                                           long pitch, const Hook& before_store = Hook()) {
   if (MODE == 1 || MODE == 2) {
     e[0] = fma(a, gu, e[0]);
     e[FS - 1] = fma(a, gd, e[FS - 1]);
@@ -365,6 +366,7 @@ __device__ __forceinline__ void fine_y_mid(double (&e)[FS], double gu, double gd
 #pragma unroll
       for (int r = 0; r < FS; ++r) e[r] = fma(bscale, bt[(long)r * pitch], e[r]);
     }
+    before_store();      // loads whose values are wanted after the stores: a load issued behind them waits for all of them
     fine_store_rows<STREAM>(dp, pitch, e);
   }
 }
@@ -482,6 +484,8 @@ struct FineOnePass {
   double* p_next;        // P of the next step, in the layout of iface[1]
   const double* wy;      // [nfield][3 y-chunk variants][2][FS] first / last rows of A_y^-1 (fine_plan_prepare)
   double* tsums;         // [nfield][px][py][4] T = (ends_f yf, ends_l yf, ends_f yl, ends_l yl) of the next step's x-rows
+  const double* xmap;    // [nfield][3 x-chunk variants][FS c'][FS c] zero-ghost x-front of the unit vector e_c', no sources
+  const double* pbias;   // [nfield][3 x-chunk variants][3 y-chunk variants][2][FS] P of an all-zero tile (the sources)
 };
 
 // what q0..q3 of y-chunk yc at column c of x-chunk tx add to P: phi_L / phi_R of the column and S of the chunks yc - 1
@@ -536,10 +540,76 @@ __device__ __forceinline__ void fine_tile_sums(const FineView& v, int b, int tx,
   tsums[(((long)b * v.px + tx) * v.py + yc) * 4 + (k >> 3)] = a;
 }
 
+// P of the next step from the y-eliminations (rf, rl) of rhs1': lane (h, c) formed those of column 32 tx + c over the rows
+// of y-chunk yc = 2 ty + h.  The zero-ghost x-front acts along the columns and is the same affine map for every row up to
+// its row source, the y-elimination is one linear form over the rows for every column, so the two commute:
+//   P_f(yc, c) = pbias_f[c] + sum_c' M[c][c'] rf(c')     (likewise _l),
+// M = op.xmap (x-front of the unit vectors), pbias = x-front and y-elimination of an all-zero tile (the sources).
+// Where the loads sit decides what the tail costs: the wave's vector-memory counter retires in order, so a load issued
+// behind the 32 row stores of the plane waits until all of them are acknowledged.  The end-row weights of fine_tile_sums
+// and the bias are therefore loaded BEFORE the stores (fine_p_prefetch, from fine_y_mid); the map, which nothing can hold
+// through the y-work and the last transpose, right after that transpose (fine_p_prefetch_map), so that its wait overlaps
+// ends32 and the tile sums.  To fit the registers free there a lane keeps half a column of the map - lane (h, c) rows
+// c' = 16 h .. 16 h + 15 of column c, both half-waves hold the same columns - and forms the partial sums of BOTH y-chunks
+// over its 16 rows; the halves then trade the partial sum the other one needs.  The 64 pairs wait in LDS behind the
+// transpose patches from the moment they exist.
+// The summation order is part of the result: per half c' ascending from zero, then (bias + rows 0..15) + rows 16..31.
+struct FinePTail {
+  double wf, wl;          // fine_tile_sums: row c of the end rows of y-chunk yc
+  double bf, bl;          // pbias of (x-variant, y-variant of yc) at column c
+  double m[FS / 2];       // xmap[16 h + k][c]
+};
+
+__device__ __forceinline__ void fine_p_prefetch(const FineView& v, const FineXTile& t, const FineOnePass& op, int va, int vb,
+                                                unsigned ln, FinePTail& p) {
+  const unsigned h = ln >> 5, c = ln & 31;
+  const int yvar = h ? vb : va;
+  const double* wr = op.wy + ((long)t.b * 3 + yvar) * 2 * FS + c;
+  p.wf = wr[0];
+  p.wl = wr[FS];
+  const long xv = (long)t.b * 3 + chunk_variant(t.tx, v.px);
+  const double* bias = op.pbias + ((xv * 3 + yvar) * 2) * FS + c;
+  p.bf = bias[0];
+  p.bl = bias[FS];
+}
+__device__ __forceinline__ void fine_p_prefetch_map(const FineView& v, const FineXTile& t, const FineOnePass& op, unsigned ln,
+                                                    FinePTail& p) {
+  const unsigned h = ln >> 5, c = ln & 31;
+  const long xv = (long)t.b * 3 + chunk_variant(t.tx, v.px);
+  const double* mt = op.xmap + xv * (FS * FS) + (h * (FS / 2)) * FS + c;
+#pragma unroll
+  for (int k = 0; k < FS / 2; ++k) p.m[k] = mt[k * FS];
+}
+
+__device__ __forceinline__ void fine_p_map(const FineView& v, const FineXTile& t, const FineOnePass& op, unsigned ln,
+                                           const FinePTail& p, const double* lds_pairs) {
+  const unsigned h = ln >> 5, c = ln & 31;
+  const double2* pairs = reinterpret_cast<const double2*>(lds_pairs) + h * (FS / 2);
+  double f0 = 0.0, l0 = 0.0, f1 = 0.0, l1 = 0.0;      // partial sums over this half's 16 rows, y-chunks 2 ty and 2 ty + 1
+#pragma unroll
+  for (int k = 0; k < FS / 2; ++k) {
+    const double2 r0 = pairs[k], r1 = pairs[FS + k];
+    f0 = fma(p.m[k], r0.x, f0);
+    l0 = fma(p.m[k], r0.y, l0);
+    f1 = fma(p.m[k], r1.x, f1);
+    l1 = fma(p.m[k], r1.y, l1);
+  }
+  // lane (h, c) keeps the partial sums of its own y-chunk and hands those of the other one to lane (1 - h, c)
+  const double gf = __shfl_xor(h ? f0 : f1, 32), gl = __shfl_xor(h ? l0 : l1, 32);
+  const double kf = h ? f1 : f0, kl = h ? l1 : l0;
+  const double pf = (p.bf + (h ? gf : kf)) + (h ? kf : gf);
+  const double pl = (p.bl + (h ? gl : kl)) + (h ? kl : gl);
+  double* ir = op.p_next + (long)t.b * (2 * v.py + 2) * v.nx + t.tx * FS + c;
+  const int yc = 2 * t.ty + h;
+  ir[(long)(2 * yc + 1) * v.nx] = pf;
+  ir[(long)(2 * yc + 2) * v.nx] = pl;
+}
+
 // The fused pass, and with ONEPASS its one-pass form F': the y-ghosts come from v.iface[1] in P form and op.sums (all
-// zeros on the first step, whose rows R left in full), and MODE 1 also forms P of the next step from the rhs1' it holds,
-// after the plane store (the x-front of fine_x_front with zero x-ghosts, without the load, and fine_x_ends) -> op.p_next,
-// and T of the x-interface rows it writes (fine_tile_sums) -> op.tsums.
+// zeros on the first step, whose rows R left in full), and MODE 1 also forms P of the next step from the rhs1' it holds:
+// its y-elimination right after the plane store, where the rows are in the layout of fine_x_ends, and the x-front of
+// those two values per lane at the end (fine_p_map) -> op.p_next, and T of the x-interface rows it writes
+// (fine_tile_sums) -> op.tsums.
 template <int MODE, int STREAM, bool ONEPASS>
 __device__ __forceinline__ void fine_fused_body(const FineView& v, double* iface0_next, double* w, double* dst,
                                                 const FineOnePass& op, double* lds) {
@@ -570,32 +640,51 @@ __device__ __forceinline__ void fine_fused_body(const FineView& v, double* iface
   const double scol = fine_col_source(v, a, col);
   asm volatile("" : "+v"(t.off));
   double* dp = dst + t.origin + t.off;
+  // One-pass form: what the tail needs from memory is loaded between the y-work and the plane stores (fine_p_prefetch), and
+  // everything the lane needs from there on (LDS patch, interface rows) is formed again from the lane index instead of
+  // living through the y-work - at the edge of three waves per SIMD that decides between no scratch and a spilled column.
+  FinePTail pt{};
+  int ln = lane;
+  auto prefetch = [&]() {
+    if (ONEPASS && MODE == 1) {
+      asm volatile("" : "+v"(ln) : "v"(e[FS - 1]));      // not before the y-work is done
+      if (!(QP_ABL & 128)) fine_p_prefetch(v, t, op, va, vb, (unsigned)ln, pt);
+      else {
+        const double* wr = op.wy + ((long)b * 3 + ((ln >> 5) ? vb : va)) * 2 * FS + (ln & 31);
+        pt.wf = wr[0];
+        pt.wl = wr[FS];
+      }
+    }
+  };
   if (va == vb) {                      // wave-uniform: interior tile rows
-    fine_y_mid<MODE, STREAM, false>(e, gu, gd, a, parts[1], a, parts[1], scol, 0.0, nullptr, dp, v.nx);
+    fine_y_mid<MODE, STREAM, false>(e, gu, gd, a, parts[1], a, parts[1], scol, 0.0, nullptr, dp, v.nx, prefetch);
   } else {
     const CoefFinePair cy{parts[1].part, parts[2].part, h != 0};
-    fine_y_mid<MODE, STREAM, false>(e, gu, gd, a, cy, a, cy, scol, 0.0, nullptr, dp, v.nx);
+    fine_y_mid<MODE, STREAM, false>(e, gu, gd, a, cy, a, cy, scol, 0.0, nullptr, dp, v.nx, prefetch);
   }
   if (MODE == 2) return;
   if (QP_ABL & 8) return;
-  double wf = 0.0, wl = 0.0;           // row c of the end rows of y-chunk yc: in flight during the transpose and ends32
-  if (ONEPASS) {
-    const double* wr = op.wy + ((long)b * 3 + (h ? vb : va)) * 2 * FS + c;
-    wf = wr[0];
-    wl = wr[FS];
+  const int hn = ln >> 5, cn = ln & 31;
+  if (ONEPASS && !(QP_ABL & 128)) {    // y-elimination of the rhs1' this lane holds, parked in LDS for fine_p_map
+    double rf, rl;
+    ends32_pair(e, v, 1, b, 2 * ty, v.py, hn, rf, rl);
+    reinterpret_cast<double2*>(lds + FINE_LDS_DOUBLES)[ln] = make_double2(rf, rl);
   }
-  transpose32h(e, lds, lane);          // lane = row 64 ty + lane, register = column of x-chunk tx
+  transpose32h(e, lds, ln);            // lane = row 64 ty + lane, register = column of x-chunk tx
+  if (ONEPASS && !(QP_ABL & 128)) {    // the half column of the map: issued here, where 32 registers are free to hold it
+    unsigned l2 = ln;
+    asm volatile("" : "+v"(l2) : "v"(e[0]));
+    fine_p_prefetch_map(v, t, op, l2, pt);
+  }
   double yf, yl;
   ends32(e, parts[3], yf, yl);
-  double* ir = iface0_next + (long)b * (2 * v.px + 2) * v.ny + ty * 64 + lane;
+  double* ir = iface0_next + (long)b * (2 * v.px + 2) * v.ny + ty * 64 + ln;
   ir[(long)(2 * tx + 1) * v.ny] = yf;
   ir[(long)(2 * tx + 2) * v.ny] = yl;
   if (ONEPASS) {     // T of these rows, then P of the next step
-    fine_tile_sums(v, b, tx, yc, c, wf, wl, yf, yl, op.tsums);
-    thomas32(e, parts[0]);
-    explicit32(e, 0.0, 0.0, parts[0], a, fine_row_source(v, a, ty * 64 + lane));
-    transpose32h(e, lds, lane);
-    fine_x_ends(v, t, e, op.p_next);
+    fine_tile_sums(v, b, tx, 2 * ty + hn, cn, pt.wf, pt.wl, yf, yl, op.tsums);
+    if (QP_ABL & 128) return;
+    fine_p_map(v, t, op, (unsigned)ln, pt, lds + FINE_LDS_DOUBLES);
   }
 }
 
@@ -608,7 +697,7 @@ __global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_fused_kernel(FineView v
 
 // One-pass step F' (MODE 1) and the exit pass of one-pass steps (MODE 2).  F' with the tile sums sits at the edge of three
 // waves per SIMD (168 VGPRs): left to itself the scheduler gives the third wave up (174 VGPRs); held to three it
-// allocates 159 without scratch.  The exit pass (132 VGPRs) is not affected.
+// allocates 167 without scratch.  The exit pass (132 VGPRs) is not affected.
 #ifdef QP_FORCE_WAVES
 #define QP_ONEPASS_WAVES_ATTR QP_WAVES_ATTR
 #else
@@ -617,7 +706,8 @@ __global__ void __launch_bounds__(64) QP_WAVES_ATTR fine_fused_kernel(FineView v
 template <int MODE, int STREAM>
 __global__ void __launch_bounds__(64) QP_ONEPASS_WAVES_ATTR fine_onepass_kernel(FineView v, double* iface0_next, double* w,
                                                                         double* dst, FineOnePass op) {
-  __shared__ double lds[FINE_LDS_DOUBLES];
+  // MODE 1: 64 pairs behind the transpose patches (FINE_LDS_PAIRS), written before the last transpose, read after it
+  __shared__ __attribute__((aligned(16))) double lds[FINE_LDS_DOUBLES + (MODE == 1 ? FINE_LDS_PAIRS : 0)];
   fine_fused_body<MODE, STREAM, true>(v, iface0_next, w, dst, op, lds);
 }
 

@@ -861,6 +861,49 @@ static void fine_end_rows(const double* tab, double* w) {       // w[2][FS]
   for (int k = FS - 2; k >= 0; --k) w[FS + k] = w[FS + k + 1] * tab[T_EAWF * FS + k + 1];
 }
 
+// x-chunk: xmap[c'][c] = entry c of the zero-ghost x-front of the unit vector e_c' without sources (thomas32, then
+// explicit32 with gl = gr = 0, T_SRC and `extra` left out) - the map M of fine_p_map, transposed
+static void fine_front_map(const double* tab, double a, double* xmap) {       // xmap[FS][FS]
+  for (int cp = 0; cp < FS; ++cp) {
+    double e[FS] = {};
+    e[cp] = 1.0;
+    double dp = 0.0;
+    for (int k = 0; k < FS; ++k) {
+      dp = std::fma(tab[T_AWF * FS + k], dp, e[k] * tab[T_W * FS + k]);
+      e[k] = dp;
+    }
+    double x = 0.0;
+    for (int k = FS - 1; k >= 0; --k) {
+      x = std::fma(tab[T_AWB * FS + k], x, e[k]);
+      e[k] = x;
+    }
+    double prev = 0.0;
+    for (int k = 0; k < FS; ++k) {
+      const double cur = e[k];
+      const double nxt = k + 1 < FS ? e[k + 1] : 0.0;
+      xmap[cp * FS + k] = std::fma(a, prev + nxt, tab[T_C0 * FS + k] * cur);
+      prev = cur;
+    }
+  }
+}
+
+// (x-chunk, y-chunk): P of an all-zero tile, the affine part of fine_p_map - the x-front leaves T_SRC in the first / last
+// column and the row source `srow` in every column, then ends32 over the rows with the y-chunk's elimination table `ytab`
+static void fine_front_bias(const double* xsrc, const double* ytab, const double* srow, double* pbias) {   // pbias[2][FS]
+  for (int c = 0; c < FS; ++c) {
+    double dp = 0.0, bp = 0.0;
+    for (int k = 0; k < FS; ++k) {
+      const int j = FS - 1 - k;
+      const double ek = (c == 0 || c == FS - 1) ? xsrc[c] + srow[k] : srow[k];
+      const double ej = (c == 0 || c == FS - 1) ? xsrc[c] + srow[j] : srow[j];
+      dp = std::fma(ytab[T_EAWF * FS + k], dp, ek);
+      bp = std::fma(ytab[T_EAV * FS + j], bp, ej);
+    }
+    pbias[c] = bp * ytab[T_EV * FS];
+    pbias[FS + c] = dp * ytab[T_EW * FS + FS - 1];
+  }
+}
+
 // Tables, interface coefficients and interface arrays of the fine tiles for step form `form`, bound into plan->fine.
 // Returns false, with nothing queued or bound, when the plan does not qualify: chunks of 32 cells not decoupled at this
 // r D, or a table without the compact form.  alpha[b] = r D_b (the caller's upload, alive until the commit).
@@ -876,12 +919,16 @@ static bool fine_plan_prepare(qp_adi_rect_plan* plan, int form, const std::vecto
   std::vector<double> icoef[2];
   for (int d = 0; d < 2; ++d) icoef[d].assign((size_t)nfield * (spec[d].P + 1) * 3, 0.0);
   std::vector<double> phi, wy;            // one-pass tables per (field, variant): x-ghost responses, A_y^-1 end rows
+  std::vector<double> xmap, pbias;        // x-front map per (field, x-variant), P of a zero tile per (field, x-, y-variant)
   if (form == STEPS_ONEPASS) {
     phi.assign((size_t)nfield * 3 * 2 * FS, 0.0);
     wy.assign((size_t)nfield * 3 * 2 * FS, 0.0);
+    xmap.assign((size_t)nfield * 3 * FS * FS, 0.0);
+    pbias.assign((size_t)nfield * 3 * 3 * 2 * FS, 0.0);
   }
   for (int b = 0; b < nfield; ++b) {
     const double a = alpha[b];
+    double xsrc[3][FS] = {};         // T_SRC of the x-chunk variants of this field, for pbias
     for (int d = 0; d < 2; ++d) {
       const int P = spec[d].P;       // >= 2: no single-chunk variant
       for (int var = 0; var < 3; ++var) {
@@ -903,8 +950,19 @@ static bool fine_plan_prepare(qp_adi_rect_plan* plan, int form, const std::vecto
         build_compact_table(FS, tab.data(), &ctab[(((size_t)d * nfield + b) * 4 + var) * 2 * CT_PART]);
         if (form == STEPS_ONEPASS) {
           const size_t o = ((size_t)b * 3 + var) * 2 * FS;
-          if (d == 0) fine_ghost_response(tab.data(), a, &phi[o]);
-          else fine_end_rows(tab.data(), &wy[o]);
+          if (d == 0) {
+            fine_ghost_response(tab.data(), a, &phi[o]);
+            fine_front_map(tab.data(), a, &xmap[((size_t)b * 3 + var) * FS * FS]);
+            std::copy(&tab[T_SRC * FS], &tab[T_SRC * FS] + FS, xsrc[var]);
+          } else {
+            fine_end_rows(tab.data(), &wy[o]);
+            double srow[FS] = {};    // fine_row_source of the rows of this y-chunk
+            if (var == 1) srow[0] = a * v.other_src[1][0];
+            if (var == 2) srow[FS - 1] = a * v.other_src[1][1];
+            for (int xv = 0; xv < 3; ++xv)
+              if (variant_chunk(xv, spec[0].P) >= 0)
+                fine_front_bias(xsrc[xv], tab.data(), srow, &pbias[(((size_t)b * 3 + xv) * 3 + var) * 2 * FS]);
+          }
         }
       }
       const double far = reduced_tables(spec[d], a, 0, P, nullptr, &icoef[d][(size_t)b * (P + 1) * 3], FS);
@@ -930,6 +988,8 @@ static bool fine_plan_prepare(qp_adi_rect_plan* plan, int form, const std::vecto
   if (form == STEPS_ONEPASS) {
     slab.upload_owned(std::move(phi), slab.mut(&fs.op.phi));
     slab.upload_owned(std::move(wy), slab.mut(&fs.op.wy));
+    slab.upload_owned(std::move(xmap), slab.mut(&fs.op.xmap));
+    slab.upload_owned(std::move(pbias), slab.mut(&fs.op.pbias));
     slab.zeros(yrows, &fs.iy_next);
     slab.zeros(nsums, &fs.sums[0]);
     slab.zeros(nsums, &fs.sums[1]);

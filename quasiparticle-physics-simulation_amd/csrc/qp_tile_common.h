@@ -88,6 +88,9 @@ __device__ __forceinline__ ctab_t as_const(const double* p) {
 #ifndef QP_ABL
 #define QP_ABL 0      // timing-only ablation builds (tools/ablate.sh): results are wrong, only the clock matters
 #endif
+// bits 0..6 are tested where the piece they remove lives (ghost loads, table loads, transposes, interface work, Thomas
+// solve, explicit operator, scalar-cache warming); bit 7 (128): the one-pass kernel returns right after fine_tile_sums,
+// i.e. forms no P of the next step (fine_fused_body) - the ceiling of any change to that tail
 
 // Where the solves get coefficient k of a slot from.  The chains need it as a wave-uniform operand at step k.
 //  * CoefCompact (every table of the plan has the compact form - all grids whose extents are multiples of 64 with

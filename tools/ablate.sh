@@ -1,7 +1,8 @@
 #!/bin/bash
 # Timing-only ablation builds of the rectangle ADI kernels: tools/bin/libqpsim_abl<N>.so with -DQP_ABL=<N>
 # (bit 0 no ghost loads, 1 constants instead of table loads, 2 no transposes, 3 no dot products / interface stores,
-#  4 no Thomas solve, 5 no explicit operator).  Results are wrong by construction; run tools/exp_shapes.py against them:
+#  4 no Thomas solve, 5 no explicit operator, 6 no scalar-cache warming, 7 the one-pass kernel returns after its tile sums:
+#  no P of the next step).  Results are wrong by construction; run tools/exp_shapes.py against them:
 #    QPSIM_HIP_LIBRARY=tools/bin/libqpsim_abl1.so python tools/exp_shapes.py 4096x4096
 set -e
 cd "$(dirname "$0")/.."
