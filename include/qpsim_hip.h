@@ -413,6 +413,24 @@ size_t qp_region_sums_workspace_bytes(int32_t nfield, int64_t ncell_member, int6
 int qp_region_sums(const double* state, const uint8_t* region_bits, int32_t nfield, int64_t ncell_member, int64_t members,
                    int32_t nregion, void* workspace, double* out, void* stream);
 
+/*
+ * Block sums (coarse frames; stands in for the frame stores of solver.py:1479-1494, reduced over bin x bin blocks).
+ * state[nfield][members][ny * nx] is the layout of the time loop, flags[ny * nx] the flag plane of ONE member grid (only
+ * QP_FLAG_ACTIVE is read).  bin = 2, 4, 8, 16, 32 or 64 is the block edge; blocks are aligned to the origin of the full
+ * frame and (oy, ox), 0 <= oy, ox < bin, is the position of device cell (0, 0) inside its block, so device cell (j, i)
+ * belongs to block ((oy + j) / bin, (ox + i) / bin).  out[members][nfield][cny][cnx], cny = ceil((oy + ny) / bin), cnx =
+ * ceil((ox + nx) / bin): every entry is written on every call, with the sum of the plane over the active cells of the
+ * block (a select, never a product: NaN or Inf outside the mask reaches no sum); a block without an active cell gives +0.0.
+ * One launch, no workspace, no LDS: a wave takes 64 frame columns (lane <-> column, 8-byte loads) and max(bin, 16) frame
+ * rows; a lane adds its column over the rows of a block top to bottom, an xor butterfly over the aligned group of bin
+ * lanes finishes the block, one lane stores it.  The partition depends on (ny, nx, oy, ox, bin) alone and there are no
+ * atomics and no completion counters: equal inputs give bitwise equal outputs, and member m of a batch gives the bits of
+ * a lone call on its slice whatever the parity of ny * nx.  Any 8-byte aligned `state` will do.  state and flags are
+ * only read.  Bandwidth-bound: 8 B per cell and field, 1 B per cell and field of flags (served by the caches).
+ */
+int qp_block_sums(const double* state, const uint8_t* flags, int32_t nfield, int32_t ny, int32_t nx, int64_t members,
+                  int32_t bin, int32_t oy, int32_t ox, double* out, void* stream);
+
 /* out[p] = sum_i state[i][p] * weights[i]  (phonon integrated occupation, solver.py:1358). */
 int qp_weighted_sum(const double* state, const double* weights, int32_t n, int64_t ncell, double* out, void* stream);
 

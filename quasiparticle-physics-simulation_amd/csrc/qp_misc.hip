@@ -331,6 +331,78 @@ static void region_partial_launch(bool vec, dim3 grid, hipStream_t stream, const
                        part);
 }
 
+// ---- block sums (coarse frames): out[m][f][cy][cx] = sum of s[f][m][j][i] over the active cells of one B x B block ----
+// Blocks are aligned to the origin of the full frame; device cell (0, 0) sits at (oy, ox) inside its block, so frame row
+// g = oy + j and frame column h = ox + i.  A wave owns frame columns [64 seg, 64 seg + 64) (lane <-> column, 8-byte loads:
+// one 512-byte segment per row) and the kBlockRows = max(B, 16) frame rows of one row group, i.e. 64 / B blocks across and
+// kBlockRows / B blocks down.  Each lane adds its column over the B rows of a block row top to bottom, starting from +0.0,
+// with the 16 loads of a round issued before the first add; an xor butterfly over the aligned group of B lanes then leaves
+// the block sum in every lane of the group, and the group's first lane stores it.  A cell enters through a select; a lane
+// outside the device grid loads the nearest cell of the plane instead (so that no load sits behind a branch) and counts +0.0.  Which lane adds which cell depends on (ny, nx, oy, ox, B)
+// alone - not on the plane - and every output has exactly one writer: no LDS, no workspace, no atomics.
+template <int B>
+__global__ void __launch_bounds__(256) block_sums_kernel(const double* __restrict__ s, const uint8_t* __restrict__ flags,
+                                                         int ny, int nx, long members, int oy, int ox, int nseg,
+                                                         int ngroup, int cny, int cnx, int nfield,
+                                                         double* __restrict__ out) {
+  constexpr int kBlockRows = B < 16 ? 16 : B;       // frame rows of a wave
+  constexpr int kDown = kBlockRows / B;             // block rows of a wave
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wave >= (long)nseg * ngroup) return;          // wave-uniform: whole waves leave
+  const int seg = (int)(wave % nseg), group = (int)(wave / nseg);
+  const long m = blockIdx.y, f = blockIdx.z;
+  const int i = seg * 64 + lane - ox;               // device column of this lane
+  const bool col_in = i >= 0 && i < nx;
+  const int ic = min(max(i, 0), nx - 1);
+  const int j0 = group * kBlockRows - oy;           // device row of the wave's first frame row
+  const double* p = s + (f * members + m) * ((long)ny * nx);
+  double acc[kDown];
+#pragma unroll
+  for (int d = 0; d < kDown; ++d) acc[d] = 0.0;
+#pragma unroll 1
+  for (int r0 = 0; r0 < kBlockRows; r0 += 16) {   // one round for B <= 16; B / 16 rounds into the one block row else
+    double v[16];
+    unsigned on[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int j = j0 + r0 + u;
+      const bool in = col_in && j >= 0 && j < ny;
+      const long c = (long)min(max(j, 0), ny - 1) * nx + ic;      // always a cell of the plane: the load needs no branch
+      v[u] = p[c];
+      on[u] = (unsigned)flags[c] & (in ? QP_FLAG_ACTIVE : 0u);
+    }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) acc[kDown == 1 ? 0 : (r0 + u) / B] += on[u] ? v[u] : 0.0;
+  }
+#pragma unroll
+  for (int d = 0; d < kDown; ++d) {
+#pragma unroll
+    for (int off = 1; off < B; off <<= 1) acc[d] += __shfl_xor(acc[d], off, 64);
+  }
+  const int cx = seg * (64 / B) + lane / B;
+  if (lane % B == 0 && cx < cnx) {
+    double* o = out + ((m * nfield + f) * cny) * (long)cnx + cx;
+#pragma unroll
+    for (int d = 0; d < kDown; ++d) {
+      const int cy = group * kDown + d;
+      if (cy < cny) o[(long)cy * cnx] = acc[d];
+    }
+  }
+}
+
+template <int B>
+static void block_sums_launch(hipStream_t stream, const double* s, const uint8_t* flags, int ny, int nx, long members,
+                              int nfield, int oy, int ox, double* out) {
+  constexpr int kBlockRows = B < 16 ? 16 : B;
+  const int cny = (oy + ny + B - 1) / B, cnx = (ox + nx + B - 1) / B;
+  const int nseg = (ox + nx + 63) / 64, ngroup = (oy + ny + kBlockRows - 1) / kBlockRows;
+  const long nwave = (long)nseg * ngroup;
+  const dim3 grid((unsigned)((nwave + 3) / 4), (unsigned)members, (unsigned)nfield);
+  hipLaunchKernelGGL((block_sums_kernel<B>), grid, dim3(256), 0, stream, s, flags, ny, nx, members, oy, ox, nseg, ngroup,
+                     cny, cnx, nfield, out);
+}
+
 __global__ void __launch_bounds__(256) absmax_partial_kernel(const double* __restrict__ a, long n, double* part) {
   double m = 0.0;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x) {
@@ -548,6 +620,28 @@ int qp_region_sums(const double* state, const uint8_t* region_bits, int32_t nfie
   hipLaunchKernelGGL(qp::region_final_kernel, dim3((unsigned)members, (unsigned)nfield), dim3(64), 0, st,
                      (const double*)part, nchunk, (int)nregion, (long)members, (int)nfield, out);
   return qp::check_launch("qp_region_sums");
+}
+
+int qp_block_sums(const double* state, const uint8_t* flags, int32_t nfield, int32_t ny, int32_t nx, int64_t members,
+                  int32_t bin, int32_t oy, int32_t ox, double* out, void* stream) {
+  QP_REQUIRE(state && flags && out, "NULL argument");
+  QP_REQUIRE(nfield > 0 && ny > 0 && nx > 0 && members > 0, "nfield, ny, nx, members must be positive");
+  QP_REQUIRE(bin == 2 || bin == 4 || bin == 8 || bin == 16 || bin == 32 || bin == 64, "bin must be 2, 4, 8, 16, 32 or 64");
+  QP_REQUIRE(oy >= 0 && oy < bin && ox >= 0 && ox < bin, "oy and ox must lie in [0, bin)");
+  QP_REQUIRE(nfield <= 65535 && members <= 65535, "at most 65535 fields and 65535 members per call");
+  QP_REQUIRE(ny <= (1 << 30) && nx <= (1 << 30), "ny and nx must not exceed 2^30");
+  // waves of one plane: 64-column segments x groups of at least 16 rows
+  QP_REQUIRE(((long)nx / 64 + 2) * ((long)ny / 16 + 2) <= 0x7fffffffL, "ny x nx too large for one launch");
+  const hipStream_t st = (hipStream_t)stream;
+  switch (bin) {
+    case 2: qp::block_sums_launch<2>(st, state, flags, ny, nx, (long)members, nfield, oy, ox, out); break;
+    case 4: qp::block_sums_launch<4>(st, state, flags, ny, nx, (long)members, nfield, oy, ox, out); break;
+    case 8: qp::block_sums_launch<8>(st, state, flags, ny, nx, (long)members, nfield, oy, ox, out); break;
+    case 16: qp::block_sums_launch<16>(st, state, flags, ny, nx, (long)members, nfield, oy, ox, out); break;
+    case 32: qp::block_sums_launch<32>(st, state, flags, ny, nx, (long)members, nfield, oy, ox, out); break;
+    default: qp::block_sums_launch<64>(st, state, flags, ny, nx, (long)members, nfield, oy, ox, out); break;
+  }
+  return qp::check_launch("qp_block_sums");
 }
 
 int qp_weighted_sum(const double* state, const double* weights, int32_t n, int64_t ncell, double* out, void* stream) {

@@ -94,6 +94,8 @@ SIGNATURES = {
     "qp_energy_integrate": (C.c_int, [c_dp, C.c_int32, C.c_int64, C.c_double, c_dp, c_dp]),
     "qp_region_sums_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
     "qp_region_sums": (C.c_int, [c_dp, c_dp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, c_dp, c_dp, c_dp]),
+    "qp_block_sums": (C.c_int, [c_dp, c_dp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                c_dp, c_dp]),
     "qp_pauli_members_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "qp_pauli_stats_members": (C.c_int, [c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double,
                                          c_dp, c_dp, c_dp, c_dp]),

@@ -166,6 +166,39 @@ def pack_region_bits(regions, grid_mask: np.ndarray, offset=(0, 0)) -> np.ndarra
     return bits
 
 
+COARSE_BINS = (2, 4, 8, 16, 32, 64)      # block edges of coarse frames (``qp_block_sums``)
+
+
+class CoarseLayout:
+    """Where the b x b blocks of coarse frames lie (``coarse_layout``): ``shape`` (cy, cx) of the full coarse frame,
+    ``cells`` [cy, cx] in-mask cells per block, ``origin`` (r0, c0) of the mask's bounding box, ``offset`` (oy, ox) of the
+    device cell (0, 0) inside its block, ``window`` (wy, wx, cny, cnx): the rows / columns of the full coarse frame that
+    the device output [cny, cnx] occupies."""
+
+    def __init__(self, bin, shape, cells, origin, offset, window):
+        self.bin, self.shape, self.cells, self.origin, self.offset, self.window = bin, shape, cells, origin, offset, window
+
+
+def coarse_layout(mask: np.ndarray, bin: int) -> CoarseLayout:
+    """Blocks of ``bin`` x ``bin`` cells aligned to the origin of the full frame of ``mask``, and the part of them that the
+    device grid (the bounding box of the mask) touches.  Host only."""
+    mask = np.asarray(mask, dtype=bool)
+    b = int(bin)
+    if mask.ndim != 2 or not mask.any():
+        raise ValueError("coarse_layout needs a 2-D mask with at least one interior cell")
+    H, W = mask.shape
+    cy, cx = -(-H // b), -(-W // b)
+    padded = np.zeros((cy * b, cx * b), dtype=np.int64)
+    padded[:H, :W] = mask
+    cells = padded.reshape(cy, b, cx, b).sum(axis=(1, 3))
+    rows, cols = np.flatnonzero(mask.any(axis=1)), np.flatnonzero(mask.any(axis=0))
+    r0, c0 = int(rows[0]), int(cols[0])
+    ny, nx = int(rows[-1]) - r0 + 1, int(cols[-1]) - c0 + 1
+    oy, ox = r0 % b, c0 % b
+    window = (r0 // b, c0 // b, -(-(oy + ny) // b), -(-(ox + nx) // b))
+    return CoarseLayout(b, (cy, cx), cells, (r0, c0), (oy, ox), window)
+
+
 # --------------------------------------------------------------------------------------------------------- #
 # device engine
 # --------------------------------------------------------------------------------------------------------- #
@@ -1128,6 +1161,19 @@ class Engine:
         ws = self.scratch("region_sums", (nbytes + 7) // 8)
         _hip.check(self.lib.qp_region_sums(_ptr(state), _ptr(bits), nfield, self.ncell, members, nregion, _ptr(ws),
                                            _ptr(out_row), self.stream), "qp_region_sums")
+
+    def block_sums(self, state, members: int, bin: int, oy: int, ox: int, out_row) -> None:
+        """out_row[m][f][cy][cx] = sum of state[f][m][cell] over the active cells of one ``bin`` x ``bin`` block
+        (``qp_block_sums``; ``(oy, ox)`` as ``coarse_layout`` gives them), ``state`` laid out [field][member][cell] and
+        ``out_row`` one [members, fields, cny, cnx] row of a caller-owned device buffer.  Enqueues one kernel on the compute
+        stream and nothing else: the sums stay on the device until the caller fetches its buffer."""
+        members, nfield = int(members), int(out_row.shape[1])
+        cny, cnx = -(-(oy + self.ny) // bin), -(-(ox + self.nx) // bin)
+        if (state.numel() != nfield * members * self.ncell or tuple(out_row.shape) != (members, nfield, cny, cnx)
+                or not out_row.is_contiguous()):
+            raise ValueError("block_sums: out_row must be a contiguous [members, fields, cny, cnx] row matching the state")
+        _hip.check(self.lib.qp_block_sums(_ptr(state), _ptr(self.d_flags), nfield, self.ny, self.nx, members, int(bin),
+                                          int(oy), int(ox), _ptr(out_row), self.stream), "qp_block_sums")
 
     def weighted_sum(self, planes, weights, ncell: int | None = None):
         """sum_k weights[k] planes[k]; ``weights`` on the host or already on the device, ``ncell`` as ``energy_integral``."""

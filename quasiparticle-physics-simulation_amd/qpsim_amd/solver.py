@@ -33,6 +33,18 @@ and only crosses PCIe at store points.  Additive keyword arguments (all optional
     dx^2 dE sum_i density (scalar mode: dx^2 density).  A sampled step is sequenced like a stored one (no fused pair pass
     across it), so its state is bit for bit the state a run with ``store_every = trace_every`` stores there.  The default
     ``trace_out=None`` runs exactly as before.
+``coarse_out``, ``coarse_bin``, ``coarse_every``
+    Coarse frames without stored frames - where the quasiparticles are as they evolve: with a dict as ``coarse_out`` the
+    sums of every energy plane over blocks of ``coarse_bin`` x ``coarse_bin`` cells (2, 4, 8, 16, 32 or 64; aligned to the
+    origin of the mask's frame) are taken on the device at t = 0, every ``coarse_every``-th step and the last step, kept
+    there, and fetched once when the run ends.  ``coarse_out`` is cleared at entry and filled on normal return with
+    ``times`` [S], ``bin``, ``cells`` [cy, cx] (in-mask cells per block, cy = ceil(H / bin), cx = ceil(W / bin)),
+    ``energy_bins`` (None in scalar mode, where NE = 1 and the plane is u), ``energy_sums`` [S, NE, cy, cx] (the device
+    sums, 0.0 in blocks the mask's bounding box does not touch), ``energy_frames`` [S, NE, cy, cx] = ``energy_sums / cells``
+    and ``frames`` [S, cy, cx] = the block mean of the integrated density, dE sum_i ``energy_sums[:, i]`` / ``cells`` (scalar
+    mode: ``energy_sums[:, 0] / cells``); both are NaN where ``cells == 0``.  A sampled step is sequenced like a stored one,
+    as for the traces; with both sinks each samples at the steps of its own cadence.  Not covered: phonon planes,
+    domain-decomposed runs, rectangular or non-power-of-two blocks.  The default ``coarse_out=None`` runs exactly as before.
 
 Table builders and helpers the reference exports from ``qpsim.solver`` are re-exported here under
 the same names.
@@ -45,7 +57,7 @@ from typing import Any, Callable
 import numpy as np
 
 from . import tables as _tb
-from .engine import BoundaryAssignmentError, DiffusionOperator, Engine, compile_geometry
+from .engine import COARSE_BINS, BoundaryAssignmentError, DiffusionOperator, Engine, coarse_layout, compile_geometry
 from .models import (
     BoundaryCondition,
     EdgeSegment,
@@ -56,7 +68,7 @@ from .models import (
 )
 from . import device_expr
 from .safe_eval import compile_safe_expression
-from .timeloop import EnergyRun, Outputs, Schedule, Tracer, energy_loop, scalar_loop
+from .timeloop import CoarseFrames, EnergyRun, Outputs, Schedule, Tracer, energy_loop, scalar_loop
 
 # names the reference exposes from qpsim.solver
 build_energy_grid = _tb.build_energy_grid
@@ -355,6 +367,74 @@ def _trace_result(plan, times, density: np.ndarray, E_bins, dx: float, dE) -> di
             "energy_bins": None if E_bins is None else np.array(E_bins, dtype=float), "density": density, "number": number}
 
 
+COARSE_BUFFER_LIMIT = 256 << 20     # bytes of the device buffer of coarse frames (samples x members x planes x cny x cnx x 8)
+
+
+class _CoarsePlan:
+    """Checked coarse-frame arguments of a run: ``bin``, ``every`` and the ``engine.CoarseLayout`` of the mask."""
+
+    def __init__(self, bin, every, layout):
+        self.bin, self.every, self.layout = bin, every, layout
+
+
+def _coarse_plan(mask: np.ndarray, wanted: bool, coarse_bin, coarse_every):
+    """The ``_CoarsePlan`` of a run, None when coarse frames are off (``wanted``: a sink was given).  ``ValueError`` naming
+    the argument for a ``coarse_bin`` that is no block edge, ``coarse_every`` < 1, and either of them set without a sink."""
+    if isinstance(coarse_bin, bool) or not isinstance(coarse_bin, (int, np.integer)) or int(coarse_bin) not in COARSE_BINS:
+        raise ValueError(f"coarse_bin must be one of {', '.join(map(str, COARSE_BINS))}, got {coarse_bin!r}.")
+    if isinstance(coarse_every, bool) or not isinstance(coarse_every, (int, np.integer)) or coarse_every < 1:
+        raise ValueError(f"coarse_every must be an integer >= 1, got {coarse_every!r}.")
+    if not wanted:
+        if int(coarse_bin) != 8:
+            raise ValueError("coarse_bin needs coarse_out: without a sink no coarse frame is taken.")
+        if int(coarse_every) != 1:
+            raise ValueError("coarse_every needs coarse_out: without a sink no coarse frame is taken.")
+        return None
+    return _CoarsePlan(int(coarse_bin), int(coarse_every), coarse_layout(mask, int(coarse_bin)))
+
+
+def _check_coarse_buffer(plan, sched: Schedule, members: int, nfield: int) -> None:
+    if plan is None:
+        return
+    cny, cnx = plan.layout.window[2:]
+    nbytes = 8 * sched.coarse_samples * members * nfield * cny * cnx
+    if nbytes > COARSE_BUFFER_LIMIT:
+        raise ValueError(f"coarse_every={plan.every}, coarse_bin={plan.bin} give a coarse-frame buffer of "
+                         f"{nbytes / 2 ** 20:.0f} MiB ({sched.coarse_samples} samples x {members} members x {nfield} planes x "
+                         f"{cny} x {cnx} blocks x 8 B), above the limit of {COARSE_BUFFER_LIMIT >> 20} MiB; use a larger "
+                         f"coarse_every or coarse_bin.")
+
+
+def _coarse_frames(eng, plan, sched: Schedule, members: int, nfield: int):
+    """The ``CoarseFrames`` of a run on ``eng`` (whose grid is the bounding box of the mask), None without a plan."""
+    if plan is None:
+        return None
+    return CoarseFrames(eng, plan.bin, plan.layout.offset, members, nfield, sched.coarse_samples)
+
+
+def _coarse_result(plan, times, sums: np.ndarray, E_bins, dE) -> dict:
+    """What ``coarse_out`` receives for one problem; ``sums`` [S, planes, cny, cnx] of that problem, as fetched.  The arrays of
+    a long run are large, so each is formed in one pass: a division by NaN marks the blocks without cells."""
+    lay = plan.layout
+    wy, wx, cny, cnx = lay.window
+    if (cny, cnx) == lay.shape:
+        energy_sums = np.ascontiguousarray(sums)
+    else:
+        energy_sums = np.zeros(sums.shape[:2] + lay.shape)
+        energy_sums[:, :, wy:wy + cny, wx:wx + cnx] = sums
+    cells = np.where(lay.cells == 0, np.nan, lay.cells.astype(float))
+    energy_frames = energy_sums / cells
+    if E_bins is None:
+        frames = energy_frames[:, 0].copy()
+    else:
+        frames = np.sum(energy_sums, axis=1)
+        frames *= dE
+        frames /= cells
+    return {"times": list(times), "bin": plan.bin, "cells": lay.cells.copy(),
+            "energy_bins": None if E_bins is None else np.array(E_bins, dtype=float), "energy_sums": energy_sums,
+            "energy_frames": energy_frames, "frames": frames}
+
+
 def _run_geometry(mask, edges, edge_conditions, dx, enable_diffusion):
     """Compiled geometry of the device grid = bounding box of the mask."""
     dev_mask, dev_edges = _crop_to_bounding_box(mask, edges)
@@ -566,19 +646,25 @@ def run_2d_crank_nicolson(
     trace_out: dict[str, Any] | None = None,
     trace_regions: dict[str, np.ndarray] | None = None,
     trace_every: int = 1,
+    coarse_out: dict[str, Any] | None = None,
+    coarse_bin: int = 8,
+    coarse_every: int = 1,
 ):
     """Run the 2-D Crank-Nicolson diffusion (+ local collisions) time loop on the GPU.
 
     Returns ``(times, frames, mass, color_limits, energy_frames_or_None, energy_bins_or_None)`` exactly
     as the reference does; ``phonon_history_out`` is cleared and filled the same way, and so is ``trace_out`` (module
-    docstring) when time traces are wanted.
+    docstring) when time traces are wanted, and ``coarse_out`` when coarse frames are.
     """
     mask, initial_field, store_every, n, tau_s_eff, tau_r_eff = _checked_run_arguments(
         mask, initial_field, diffusion_coefficient, dt, total_time, store_every, enable_diffusion, enable_recombination,
         enable_scattering, tau_0, tau_s, tau_r, external_generation, phonon_history_out)
     trace = _trace_plan(mask, trace_out is not None, trace_regions, trace_every)
+    coarse = _coarse_plan(mask, coarse_out is not None, coarse_bin, coarse_every)
     if trace_out is not None:
         trace_out.clear()
+    if coarse_out is not None:
+        coarse_out.clear()
     device_expr.reset_run_stats()
 
     # Device grid = bounding box of the mask.  Interior cells keep their argwhere (row-major) order under the crop, so
@@ -586,19 +672,24 @@ def run_2d_crank_nicolson(
     # mask whose interior is a solid rectangle inside a padded frame (the reference's built-in geometry) thereby
     # becomes a full rectangle on the device and takes the tiled ADI path.
     geom = _run_geometry(mask, edges, edge_conditions, dx, enable_diffusion)
-    sched = Schedule(total_time, dt, store_every, None if trace is None else trace.every)
+    sched = Schedule(total_time, dt, store_every, None if trace is None else trace.every,
+                     coarse_every=None if coarse is None else coarse.every)
     nplanes = num_energy_bins if energy_gap > 0.0 else 1
     _check_trace_buffer(trace, sched, 1, nplanes)
+    _check_coarse_buffer(coarse, sched, 1, nplanes)
     eng = Engine(geom, device=device)
     eng.pin_stream()          # one stream for the whole run: skip the per-launch lookup
     out = Outputs(mask, dx, [progress_callback])
     tracer = _tracer(eng, mask, trace, sched, 1, nplanes)
+    coarser = _coarse_frames(eng, coarse, sched, 1, nplanes)
 
     if not energy_gap > 0.0:
         result = _run_scalar(eng, sched, out, [initial_field], [diffusion_coefficient], enable_diffusion, [bath_temperature],
-                             [phonon_history_out], diffusion_scheme, cn_rtol, tracer)[0]
+                             [phonon_history_out], diffusion_scheme, cn_rtol, tracer, coarser)[0]
         if tracer is not None:
             trace_out.update(_trace_result(trace, tracer.times, tracer.density()[:, 0], None, dx, None))
+        if coarser is not None:
+            coarse_out.update(_coarse_result(coarse, coarser.times, coarser.sums()[:, 0], None, None))
         return result
 
     # ------------------------------------------------------------------ energy-resolved mode
@@ -631,7 +722,7 @@ def run_2d_crank_nicolson(
     run.physics = (enable_recombination, enable_scattering, not freeze_phonon_dynamics)
     run.generation = _Generation(external_generation, mask, E_bins, on_device=generation_on_device)
     run.verdict = _guard_rule(eng, mask, E_bins, enforce_pauli, pauli_warn_threshold, pauli_error_threshold)
-    run.tracer = tracer
+    run.tracer, run.coarse = tracer, coarser
 
     collisions = bool(enable_recombination or enable_scattering)
     energy_loop(run, sched, diffuser, collisions=collisions,
@@ -645,6 +736,8 @@ def run_2d_crank_nicolson(
         phonon_history_out.update(_dynamic_phonon_history(out, 0, omega_bins))
     if tracer is not None:
         trace_out.update(_trace_result(trace, tracer.times, tracer.density()[:, 0], E_bins, dx, dE))
+    if coarser is not None:
+        coarse_out.update(_coarse_result(coarse, coarser.times, coarser.sums()[:, 0], E_bins, dE))
     return out.times, out.frames[0], out.mass[0], _color_limits(out.frames[0]), out.energy_frames[0], E_bins
 
 
@@ -807,9 +900,10 @@ def _dynamic_phonon_history(out: Outputs, m: int, omega_bins) -> dict:
 
 
 def _run_scalar(eng: Engine, sched, out: Outputs, inits, coefficients, enable_diffusion, bath_temperatures, histories,
-                scheme, rtol, tracer=None) -> list:
+                scheme, rtol, tracer=None, coarse=None) -> list:
     """Legacy scalar mode, energy_gap == 0 (solver.py:1517-1587), for M members as one [M, ncell] field set; the result
-    tuple of every member.  ``tracer``: the time traces of the M fields (one plane per member), read by the caller."""
+    tuple of every member.  ``tracer`` / ``coarse``: the time traces / coarse frames of the M fields (one plane per member),
+    read by the caller."""
     mask, M = out.mask, out.members
     u_host = np.stack([f[mask].astype(float) for f in inits])
     u = eng.upload_packed(u_host)
@@ -817,7 +911,7 @@ def _run_scalar(eng: Engine, sched, out: Outputs, inits, coefficients, enable_di
                 if enable_diffusion else None)
     out.add_host_frames(0.0, [reconstruct_field(mask, v) for v in u_host],
                         [float(np.sum(v) * out.dx * out.dx) for v in u_host])
-    scalar_loop(sched, diffuser, u, out, eng, tracer)
+    scalar_loop(sched, diffuser, u, out, eng, tracer, coarse)
     for T_bath, history in zip(bath_temperatures, histories):
         if history is not None:
             f, ef, bins, meta = build_fixed_phonon_history(mask=mask, times=out.times, bath_temperature=T_bath,

@@ -13,6 +13,10 @@ them the region sums of every plane of the state into one row of a device buffer
 sampled step is sequenced exactly like a stored one (no pair pass across it, the stretch of diffusion steps ends there, the
 guard is read), so the state it sees is the state a run with ``store_every = trace_every`` stores there; it downloads no
 frame.  Without a tracer no step is sampled and both loops issue exactly the calls they issued before.
+
+Coarse frames (opt-in) work the same way one level up in size: a ``Schedule`` with ``coarse_every`` names its own sampled
+steps, and a ``CoarseFrames`` enqueues at each of them the b x b block sums of every plane into one row of its device buffer.
+A step sampled by either cadence is sequenced as above; each sampler is called at the steps of its own cadence only.
 """
 from __future__ import annotations
 
@@ -30,24 +34,40 @@ def _step_plan(total_time: float, dt: float) -> tuple[int, float, int]:
 
 class Schedule:
     """Step sizes and store points of a run: ``full_steps`` steps of ``dt``, then one of ``rem`` if that is positive.
-    ``trace_every`` (None: no traces) adds the sampled steps of a time trace: every ``trace_every``-th and the last."""
+    ``trace_every`` (None: no traces) adds the sampled steps of a time trace: every ``trace_every``-th and the last;
+    ``coarse_every`` (None: no coarse frames) in the same way those of the coarse frames."""
 
-    def __init__(self, total_time: float, dt: float, store_every: int, trace_every: int | None = None):
-        self.dt, self.store_every, self.trace_every = dt, store_every, trace_every
+    def __init__(self, total_time: float, dt: float, store_every: int, trace_every: int | None = None,
+                 coarse_every: int | None = None):
+        self.dt, self.store_every, self.trace_every, self.coarse_every = dt, store_every, trace_every, coarse_every
         self.full_steps, self.rem, self.total_steps = _step_plan(total_time, dt)
 
     def stored(self, step: int) -> bool:
         return step % self.store_every == 0 or step == self.total_steps
 
+    def _on(self, every: int | None, step: int) -> bool:
+        return every is not None and (step % every == 0 or step == self.total_steps)
+
+    def _rows(self, every: int | None) -> int:
+        if every is None:
+            return 0
+        return 1 + self.total_steps // every + (1 if self.total_steps % every else 0)
+
     def sampled(self, step: int) -> bool:
-        return self.trace_every is not None and (step % self.trace_every == 0 or step == self.total_steps)
+        return self._on(self.trace_every, step)
+
+    def coarse_sampled(self, step: int) -> bool:
+        return self._on(self.coarse_every, step)
 
     @property
     def samples(self) -> int:
         """Rows of a trace: t = 0 and every sampled step."""
-        if self.trace_every is None:
-            return 0
-        return 1 + self.total_steps // self.trace_every + (1 if self.total_steps % self.trace_every else 0)
+        return self._rows(self.trace_every)
+
+    @property
+    def coarse_samples(self) -> int:
+        """Coarse frames of a run: t = 0 and every step of the coarse cadence."""
+        return self._rows(self.coarse_every)
 
     def dt_of(self, step: int) -> float:
         return self.rem if step > self.full_steps else self.dt
@@ -167,18 +187,42 @@ class Tracer:
         return self.buffer[:len(self.times)].cpu().numpy()
 
 
-def scalar_loop(sched: Schedule, diffuser, u, out: Outputs, eng, tracer: Tracer | None = None) -> None:
+class CoarseFrames:
+    """Coarse frames of M members: at every sample the sums of each plane [field][member][cell] over ``bin`` x ``bin`` blocks
+    (``Engine.block_sums``; ``offset`` = (oy, ox) of ``engine.coarse_layout``) go into row k of a device buffer
+    [samples, M, fields, cny, cnx]; nothing is read back before ``sums()``."""
+
+    def __init__(self, eng, bin: int, offset, members: int, nfield: int, samples: int):
+        self.eng, self.bin, self.offset, self.members = eng, int(bin), (int(offset[0]), int(offset[1])), members
+        cny, cnx = -(-(self.offset[0] + eng.ny) // self.bin), -(-(self.offset[1] + eng.nx) // self.bin)
+        self.buffer = eng.empty(samples, members, nfield, cny, cnx)
+        self.times: list[float] = []
+
+    def sample(self, t: float, state) -> None:
+        self.eng.block_sums(state, self.members, self.bin, self.offset[0], self.offset[1], self.buffer[len(self.times)])
+        self.times.append(float(t))
+
+    def sums(self) -> np.ndarray:
+        """[samples taken, M, fields, cny, cnx] on the host (the one transfer of the coarse frames)."""
+        return self.buffer[:len(self.times)].cpu().numpy()
+
+
+def scalar_loop(sched: Schedule, diffuser, u, out: Outputs, eng, tracer: Tracer | None = None,
+                coarse: CoarseFrames | None = None) -> None:
     """Legacy scalar mode, energy_gap == 0 (solver.py:1540-1555): nothing happens between two store points (or sampled
-    steps of ``tracer``) but diffusion steps, which ``diffuser.advance`` takes in one go."""
+    steps of ``tracer`` / ``coarse``) but diffusion steps, which ``diffuser.advance`` takes in one go."""
     t = 0.0
     done = 0
     if tracer is not None:
         tracer.sample(0.0, u)
+    if coarse is not None:
+        coarse.sample(0.0, u)
     for step in range(1, sched.total_steps + 1):
         t += sched.dt_of(step)                        # same accumulation order as the reference
         stored = sched.stored(step)
         sampled = tracer is not None and sched.sampled(step)
-        if stored or sampled:
+        coarsed = coarse is not None and sched.coarse_sampled(step)
+        if stored or sampled or coarsed:
             if diffuser is not None:
                 diffuser.advance(u, done + 1, step, sched.full_steps)
             done = step
@@ -187,6 +231,8 @@ def scalar_loop(sched: Schedule, diffuser, u, out: Outputs, eng, tracer: Tracer 
             out.add_integrated(t, _device_frames_async(eng, u, out.mask))
         if sampled:
             tracer.sample(t, u)
+        if coarsed:
+            coarse.sample(t, u)
     out.lazy.flush()
 
 
@@ -201,9 +247,11 @@ class EnergyRun:
     ``guard_launch()``                                 the guard of ``state`` on its own; its ticket
     ``guard_check(ticket, step, t)``                   reads a ticket; warns / raises with the step and time it belongs to
 
-    ``tracer``: the ``Tracer`` of the run, None (the default) without time traces.
+    ``tracer``: the ``Tracer`` of the run, None (the default) without time traces; ``coarse``: its ``CoarseFrames``, None
+    (the default) without coarse frames.
     """
     tracer: Tracer | None = None
+    coarse: CoarseFrames | None = None
 
     def __init__(self, eng, out: Outputs, state, state_alt, phonon, dE: float, phonon_widths=None):
         self.eng, self.out = eng, out
@@ -241,10 +289,10 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
     ``pair_ok``: Strang steps that follow one another without a store point in between run the closing half-step of step k
     and the opening half-step of step k + 1 as ONE pass over the state (``run.collide_pair``); ``opened`` says that the
     generation term and the first half-step of the step now starting were already applied by that pass.
-    A sampled step of ``run.tracer`` ends a stretch exactly as a stored one does (``halt``) and enqueues the region sums of
-    the state instead of a download."""
+    A sampled step of ``run.tracer`` or ``run.coarse`` ends a stretch exactly as a stored one does (``halt``) and enqueues
+    the region sums / block sums of the state instead of a download."""
     pending: list = []
-    tracer = run.tracer
+    tracer, coarse = run.tracer, run.coarse
 
     def guard_flush(keep: int = 0) -> None:
         while len(pending) > keep:
@@ -266,6 +314,8 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
     run.store(0.0)
     if tracer is not None:
         tracer.sample(0.0, run.state)
+    if coarse is not None:
+        coarse.sample(0.0, run.state)
     times = run.out.times
     t = 0.0
     done = 0
@@ -275,7 +325,8 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
         dt_step = sched.dt_of(step)
         stored = sched.stored(step)
         sampled = tracer is not None and sched.sampled(step)
-        halt = stored or sampled
+        coarsed = coarse is not None and sched.coarse_sampled(step)
+        halt = stored or sampled or coarsed
         if batch_diffusion:
             t += dt_step
             if halt:
@@ -286,6 +337,8 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
                 run.store(t)
             if sampled:
                 tracer.sample(t, run.state)
+            if coarsed:
+                coarse.sample(t, run.state)
             continue
         if not opened:
             run.generate(t, dt_step)
@@ -318,5 +371,7 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
             run.store(t)
         if sampled:
             tracer.sample(t, run.state)
+        if coarsed:
+            coarse.sample(t, run.state)
     guard_flush()
     run.out.lazy.flush()
