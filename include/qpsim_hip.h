@@ -92,6 +92,16 @@ int qp_stencil_combine(const qp_grid_desc* g, double r, const double* u, const d
 int qp_stencil_combine_norm(const qp_grid_desc* g, double r, const double* u, const double* rin, double* out,
                             double c0, double cx, double cy, double cs, double cr, void* workspace, double* norm_out,
                             void* stream);
+/* The same with one norm per field: norms_out[f] = max |out| of field f, f < nfield (the blocks of the pass never leave
+ * their field, so the per-plane norms cost no pass of their own).  The exact-CN iteration accepts plane by plane -
+ * max_f (max |res_f| / max |R_f|) <= rtol - so that a plane many decades below the largest one is solved too (a residual
+ * below DBL_MIN counts as zero there, so a plane whose right-hand side lies below about DBL_MIN / rtol, 2e-295 at 1e-13,
+ * is in effect not held to rtol).  Any field count: beyond the 1024 partial slots of the workspace the pass and its
+ * per-field finish run in launches of at most 1024 fields; qp_stencil_combine(_norm) stay one launch whose blocks stride
+ * over the fields. */
+int qp_stencil_combine_norms(const qp_grid_desc* g, double r, const double* u, const double* rin, double* out,
+                             double c0, double cx, double cy, double cs, double cr, void* workspace, double* norms_out,
+                             void* stream);
 
 /*
  * Implicit sweep: solve (I - r L_dir) x = rhs along every grid line of every field (dir 0 = x, 1 = y).
@@ -499,6 +509,10 @@ int qp_adi_rect_steps(qp_adi_rect_plan* plan, double* u, int32_t nsteps, void* s
  * norm_out is given: only the norm is formed (the residual CHECK after a Peaceman-Rachford cycle: one plane less to move). */
 int qp_adi_rect_combine(qp_adi_rect_plan* plan, const double* u, const double* rin, double* out, double c0, double cx,
                         double cy, double cs, double cr, void* workspace, double* norm_out, void* stream);
+/* The same with norms_out[f] = max |out| of field f, f < nfield (see qp_stencil_combine_norms; any field count, launches
+ * of at most 1024 fields); `out` may be NULL. */
+int qp_adi_rect_combine_norms(qp_adi_rect_plan* plan, const double* u, const double* rin, double* out, double c0, double cx,
+                              double cy, double cs, double cr, void* workspace, double* norms_out, void* stream);
 /* x[nfield][ny*nx] <- (I - a Ly)^-1 (I - a Lx)^-1 x in place: the ADI factorisation applied as the preconditioner of
  * the exact Crank-Nicolson iteration (replaces two qp_implicit_sweep calls on full rectangles). */
 int qp_adi_rect_solve(qp_adi_rect_plan* plan, double* x, void* stream);

@@ -654,8 +654,12 @@ __global__ void __launch_bounds__(256) rect_combine_kernel(int ny, int nx, int n
                                                            RectSides g, const double* __restrict__ u,
                                                            const double* __restrict__ rin, double* __restrict__ out,
                                                            double c0, double cx, double cy, double cs, double cr,
-                                                           double* __restrict__ part) {
+                                                           double* __restrict__ part, int lanes) {
   const long ncell = (long)ny * nx;
+  // the grid is `lanes` x (blocks per lane); the blocks of lane l walk fields l, l + lanes, ...  With lanes == nfield a
+  // block stays inside field b, so part[b * per + k] are that field's maxima; fewer lanes than fields (more fields than
+  // partial slots) serve the single norm and the plain combine at any field count
+  const int per = gridDim.x / lanes, lane = blockIdx.x / per;
   double m = 0.0;
   auto cell = [&](double a, int i, int j, double um, double up, double upp, double uu, double ud) {
     double lx = 0.0, ly = 0.0, src = 0.0;
@@ -671,9 +675,10 @@ __global__ void __launch_bounds__(256) rect_combine_kernel(int ny, int nx, int n
     // as two 16-byte loads per thread, the two cells beside the strip as 8-byte loads (cache hits) - no per-cell division.
     const int bands_per_field = (ny + RB - 1) / RB;
     const int chunk = 4 * blockDim.x, chunks = (nx + chunk - 1) / chunk;      // column chunks of one strip per thread
-    for (long item = blockIdx.x; item < (long)nfield * bands_per_field * chunks; item += gridDim.x) {
-      const int band = (int)(item / chunks), ch = (int)(item - (long)band * chunks);
-      const int b = band / bands_per_field, j0 = (band - b * bands_per_field) * RB;
+    for (int b = lane; b < nfield; b += lanes)
+    for (int item = blockIdx.x - lane * per; item < bands_per_field * chunks; item += per) {
+      const int band = item / chunks, ch = item - band * chunks;
+      const int j0 = band * RB;
       const double a = alpha[b];
       const double* ub0 = u + (long)b * ncell;
       const int i = ch * chunk + 4 * threadIdx.x;
@@ -718,8 +723,8 @@ __global__ void __launch_bounds__(256) rect_combine_kernel(int ny, int nx, int n
     }
   } else {
     // a block walks (field, row) pairs, its threads the cells of the row
-    for (int line = blockIdx.x; line < nfield * ny; line += gridDim.x) {
-      const int b = line / ny, j = line - b * ny;
+    for (int b = lane; b < nfield; b += lanes)
+    for (int j = blockIdx.x - lane * per; j < ny; j += per) {
       const double a = alpha[b];
       const double* ub = u + (long)b * ncell + (long)j * nx;
       const long t0 = (long)b * ncell + (long)j * nx;
@@ -1322,8 +1327,9 @@ int qp_adi_rect_solve(qp_adi_rect_plan* plan, double* x, void* stream_) {
 
 // out = c0 u + cx (a Lx u) + cy (a Ly u) + cs a S + cr rin with the plan's operator (see rect_combine_kernel); with
 // norm_out non-NULL also norm_out[0] = max |out| (workspace: qp_pauli_workspace_bytes() bytes).
-int qp_adi_rect_combine(qp_adi_rect_plan* plan, const double* u, const double* rin, double* out, double c0, double cx,
-                        double cy, double cs, double cr, void* workspace, double* norm_out, void* stream_) {
+static int rect_combine_launch(qp_adi_rect_plan* plan, const double* u, const double* rin, double* out, double c0, double cx,
+                               double cy, double cs, double cr, void* workspace, double* norm_out, bool per_field,
+                               void* stream_) {
   QP_REQUIRE(plan && u, "plan and u must be non-NULL");
   QP_REQUIRE(out || norm_out, "out may be NULL only when the norm is wanted (norm_out)");
   QP_REQUIRE(cr == 0.0 || rin, "rin is required when cr != 0");
@@ -1337,9 +1343,7 @@ int qp_adi_rect_combine(qp_adi_rect_plan* plan, const double* u, const double* r
   // block (1024^2: 128 blocks).  16-row bands were measured at 4096^2: no gain (the kernel is not bound by the halo rows).
   const bool small = (long)v.d.nfield * plan->ncell < (1L << 22);
   const int rb = small ? 4 : 8;
-  long blocks = (v.d.nx & 3) == 0 ? (long)v.d.nfield * ((v.d.ny + rb - 1) / rb) * ((v.d.nx + 1023) / 1024)
-                                  : (long)v.d.nfield * v.d.ny;
-  if (blocks > 1024) blocks = 1024;         // = the partial slots of the reduction workspace
+  long items = (v.d.nx & 3) == 0 ? (long)((v.d.ny + rb - 1) / rb) * ((v.d.nx + 1023) / 1024) : (long)v.d.ny;   // per field
   QP_REQUIRE((v.d.nx & 3) != 0 || ((uintptr_t)u | (uintptr_t)out | (uintptr_t)rin) % 16 == 0,
              "u, rin, out must be 16-byte aligned when nx is a multiple of 4");
   RectSides g{plan->bc_diag[0], plan->bc_diag[1], plan->bc_diag[2], plan->bc_diag[3],
@@ -1347,14 +1351,43 @@ int qp_adi_rect_combine(qp_adi_rect_plan* plan, const double* u, const double* r
   if (v.d.nx == 1) { g.dr = 0.0; g.sr = 0.0; }   // one column: rect_side_terms folds both x-faces into the "left" slot
   if (v.d.ny == 1) { g.dd = 0.0; g.sd = 0.0; }
   double* part = (out == nullptr || norm_out) ? (double*)workspace : nullptr;
-  with_bool(out != nullptr, [&](auto STORE) {
-    with_bool(small, [&](auto SMALL) {
-      hipLaunchKernelGGL((rect_combine_kernel<decltype(STORE)::value, decltype(SMALL)::value ? 4 : 8>), dim3((unsigned)blocks),
-                         dim3(256), 0, stream, v.d.ny, v.d.nx, v.d.nfield, v.alpha, g, u, rin, out, c0, cx, cy, cs, cr, part);
+  // 1024 = the partial slots of the reduction workspace.  Per-field norms: groups of at most 1024 fields, one lane per
+  // field, finished group by group (the slots are reused: same stream); otherwise one launch whose lanes stride over
+  // the fields
+  const int nfield = v.d.nfield;
+  const int group = (norm_out && per_field && nfield > 1024) ? 1024 : nfield;
+  for (int f0 = 0; f0 < nfield; f0 += group) {
+    const int nf = nfield - f0 < group ? nfield - f0 : group;
+    const long lanes = nf < 1024 ? nf : 1024;
+    const long per = items < 1024 / lanes ? items : 1024 / lanes;
+    const long blocks = per * lanes;
+    const long off = (long)f0 * plan->ncell;
+    with_bool(out != nullptr, [&](auto STORE) {
+      with_bool(small, [&](auto SMALL) {
+        hipLaunchKernelGGL((rect_combine_kernel<decltype(STORE)::value, decltype(SMALL)::value ? 4 : 8>),
+                           dim3((unsigned)blocks), dim3(256), 0, stream, v.d.ny, v.d.nx, nf, v.alpha + f0, g, u + off,
+                           rin ? rin + off : nullptr, out ? out + off : nullptr, c0, cx, cy, cs, cr, part, (int)lanes);
+      });
     });
-  });
-  if (norm_out) absmax_finish((const double*)workspace, (int)blocks, norm_out, stream);
+    if (norm_out && per_field) {
+      absmax_finish_fields((const double*)workspace, nf, (int)per, norm_out + f0, stream);
+    } else if (norm_out) {
+      absmax_finish((const double*)workspace, (int)blocks, norm_out, stream);
+    }
+  }
   return check_launch("qp_adi_rect_combine");
+}
+
+int qp_adi_rect_combine(qp_adi_rect_plan* plan, const double* u, const double* rin, double* out, double c0, double cx,
+                        double cy, double cs, double cr, void* workspace, double* norm_out, void* stream) {
+  return rect_combine_launch(plan, u, rin, out, c0, cx, cy, cs, cr, workspace, norm_out, false, stream);
+}
+
+// The same with norms_out[0 .. nfield) = max |out| of each field.
+int qp_adi_rect_combine_norms(qp_adi_rect_plan* plan, const double* u, const double* rin, double* out, double c0, double cx,
+                              double cy, double cs, double cr, void* workspace, double* norms_out, void* stream) {
+  QP_REQUIRE(norms_out, "norms_out must be non-NULL");
+  return rect_combine_launch(plan, u, rin, out, c0, cx, cy, cs, cr, workspace, norms_out, true, stream);
 }
 
 // Boundary rows of the reduced right-hand sides <-> contiguous [nfield][nlines] buffers (domain decomposition).

@@ -71,6 +71,9 @@ void pauli_finish_members(const PauliPartial* parts, long ncell_member, long mem
 
 // out[0] = max over `nparts` per-block maxima (second stage of qp_absmax, shared with qp_adi_rect_combine)
 void absmax_finish(const double* parts, int nparts, double* out, hipStream_t stream);
+// out[f] = max over the `per` maxima of field f, parts laid out [nfield][per] (the combine kernels keep a block inside one
+// field): the per-plane norms of the exact-CN stopping rule, no pass of their own
+void absmax_finish_fields(const double* parts, int nfield, int per, double* out, hipStream_t stream);
 
 // Harmonic-mean face diffusivity (solver.py:283).
 __device__ __forceinline__ double face_mean(double dp, double dq) {

@@ -44,15 +44,20 @@ int validate_grid(const qp_grid_desc* g, const char* who) {
 // A block walks (field, row) pairs, its threads the cells of the row (no 64-bit division per cell).  Boundary terms are
 // read only where a link is missing - they belong to boundary faces, and a cell with all four links has none - which
 // saves 32 of the 57 B per cell this kernel moved on masks that are mostly interior.  `part` non-NULL: every block leaves
-// max |out| of its cells there (NaN propagates as +inf).
+// max |out| of its cells there (NaN propagates as +inf).  The grid is `lanes` x (blocks per lane); the blocks of lane l
+// walk fields l, l + lanes, ...  With lanes == nfield a block stays inside one field, so part[b * blocks_per_lane + k] are
+// the maxima of field b: the per-plane norms need no pass of their own.  Fewer lanes than fields (more fields than partial
+// slots) serve the single norm and the plain combine at any field count.
 __global__ void __launch_bounds__(256) stencil_combine_kernel(GridView g, double r, const double* __restrict__ u,
                                                               const double* __restrict__ rin,
                                                               double* __restrict__ out, double c0, double cx,
-                                                              double cy, double cs, double cr, double* __restrict__ part) {
+                                                              double cy, double cs, double cr, double* __restrict__ part,
+                                                              int lanes) {
   const long ncell = (long)g.ny * g.nx;
   double m = 0.0;
-  for (int line = blockIdx.x; line < g.nfield * g.ny; line += gridDim.x) {
-    const int b = line / g.ny, j = line - b * g.ny;
+  const int per = gridDim.x / lanes, lane = blockIdx.x / per;
+  for (int b = lane; b < g.nfield; b += lanes)
+  for (int j = blockIdx.x - lane * per; j < g.ny; j += per) {
     const double* ub = u + (long)b * ncell;
     for (int i = threadIdx.x; i < g.nx; i += blockDim.x) {
       const long p = (long)j * g.nx + i;
@@ -149,22 +154,52 @@ int qp_version(void) { return 200; }
 
 const char* qp_last_error(void) { return qp::g_err; }
 
-int qp_stencil_combine_norm(const qp_grid_desc* g, double r, const double* u, const double* rin, double* out, double c0,
-                            double cx, double cy, double cs, double cr, void* workspace, double* norm_out, void* stream) {
+// per_field: norm_out[0 .. nfield) = max |out| of each field instead of norm_out[0] = max |out| of all of them
+static int stencil_combine_launch(const qp_grid_desc* g, double r, const double* u, const double* rin, double* out,
+                                  double c0, double cx, double cy, double cs, double cr, void* workspace, double* norm_out,
+                                  bool per_field, void* stream) {
   int rc = qp::validate_grid(g, "qp_stencil_combine");
   if (rc) return rc;
   QP_REQUIRE(u && out, "u and out must be non-NULL");
   QP_REQUIRE(rin || cr == 0.0, "rin is NULL but cr != 0");
   QP_REQUIRE(u != out, "u and out must not alias (neighbour reads)");
   QP_REQUIRE(norm_out == nullptr || workspace, "workspace is required with norm_out");
-  long blocks = (long)g->ny * g->nfield;
   const long cap = norm_out ? 1024 : 8192;           // with a norm: the partial slots of the reduction workspace
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(qp::stencil_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                     qp::make_view(g), r, u, cr == 0.0 ? nullptr : rin, out, c0, cx, cy, cs, cr,
-                     norm_out ? (double*)workspace : nullptr);
-  if (norm_out) qp::absmax_finish((const double*)workspace, (int)blocks, norm_out, (hipStream_t)stream);
+  const long ncell = (long)g->ny * g->nx;
+  // per-field norms: groups of at most `cap` fields, one lane per field, finished group by group (the partial slots are
+  // reused: same stream); otherwise one launch whose lanes stride over the fields
+  const int group = (norm_out && per_field && g->nfield > cap) ? (int)cap : g->nfield;
+  for (int f0 = 0; f0 < g->nfield; f0 += group) {
+    qp::GridView v = qp::make_view(g);
+    v.nfield = g->nfield - f0 < group ? g->nfield - f0 : group;
+    if (v.dcoef) v.dcoef += f0;
+    if (v.dfield) v.dfield += (long)f0 * ncell;
+    const long lanes = v.nfield < cap ? v.nfield : cap;
+    long per = cap / lanes;
+    if (per > g->ny) per = g->ny;
+    const long blocks = per * lanes;
+    const double* rg = cr == 0.0 ? nullptr : rin + (long)f0 * ncell;
+    hipLaunchKernelGGL(qp::stencil_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, v, r,
+                       u + (long)f0 * ncell, rg, out + (long)f0 * ncell, c0, cx, cy, cs, cr,
+                       norm_out ? (double*)workspace : nullptr, (int)lanes);
+    if (norm_out && per_field) {
+      qp::absmax_finish_fields((const double*)workspace, v.nfield, (int)per, norm_out + f0, (hipStream_t)stream);
+    } else if (norm_out) {
+      qp::absmax_finish((const double*)workspace, (int)blocks, norm_out, (hipStream_t)stream);
+    }
+  }
   return qp::check_launch("qp_stencil_combine");
+}
+
+int qp_stencil_combine_norm(const qp_grid_desc* g, double r, const double* u, const double* rin, double* out, double c0,
+                            double cx, double cy, double cs, double cr, void* workspace, double* norm_out, void* stream) {
+  return stencil_combine_launch(g, r, u, rin, out, c0, cx, cy, cs, cr, workspace, norm_out, false, stream);
+}
+
+int qp_stencil_combine_norms(const qp_grid_desc* g, double r, const double* u, const double* rin, double* out, double c0,
+                             double cx, double cy, double cs, double cr, void* workspace, double* norms_out, void* stream) {
+  QP_REQUIRE(norms_out, "norms_out must be non-NULL");
+  return stencil_combine_launch(g, r, u, rin, out, c0, cx, cy, cs, cr, workspace, norms_out, true, stream);
 }
 
 int qp_stencil_combine(const qp_grid_desc* g, double r, const double* u, const double* rin, double* out, double c0,

@@ -437,6 +437,25 @@ void absmax_finish(const double* parts, int nparts, double* out, hipStream_t str
   hipLaunchKernelGGL(absmax_final_kernel, dim3(1), dim3(256), 0, stream, parts, nparts, out);
 }
 
+// per-field finish: block f reduces the `per` maxima its field's blocks left (parts [nfield][per]) to out[f]
+__global__ void __launch_bounds__(256) absmax_fields_kernel(const double* part, int per, double* out) {
+  const double* p = part + (long)blockIdx.x * per;
+  double m = 0.0;
+  for (int k = threadIdx.x; k < per; k += blockDim.x) m = fmax(m, p[k]);
+  __shared__ double sm[256];
+  sm[threadIdx.x] = m;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) sm[threadIdx.x] = fmax(sm[threadIdx.x], sm[threadIdx.x + s]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = sm[0];
+}
+
+void absmax_finish_fields(const double* parts, int nfield, int per, double* out, hipStream_t stream) {
+  hipLaunchKernelGGL(absmax_fields_kernel, dim3((unsigned)nfield), dim3(256), 0, stream, parts, per, out);
+}
+
 // direction and iterate update of the Chebyshev iteration in one pass: d = c1 z + c2 d (d not read when c2 == 0), v += d
 __global__ void __launch_bounds__(256) cheb_update_kernel(long n, double c1, const double* __restrict__ z, double c2,
                                                           double* __restrict__ d, double* __restrict__ v) {

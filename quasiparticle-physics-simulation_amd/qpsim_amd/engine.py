@@ -202,6 +202,9 @@ def coarse_layout(mask: np.ndarray, bin: int) -> CoarseLayout:
 # --------------------------------------------------------------------------------------------------------- #
 # device engine
 # --------------------------------------------------------------------------------------------------------- #
+_TINY = float(np.finfo(np.float64).tiny)
+
+
 def _ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
 
@@ -610,10 +613,21 @@ class Engine:
         return float(plane.sum().item())
 
     # -- diffusion --------------------------------------------------------------------------------------------
-    def stencil(self, op: DiffusionOperator, u, out, c0, cx, cy, cs, rin=None, cr=0.0, norm_out=None):
-        """out = c0 u + cx rLx u + cy rLy u + cs rD S + cr rin; with ``norm_out`` (device scalar) also max |out|.  Full
-        rectangles with one boundary condition per side use the plan's own operator (no per-cell geometry arrays); other
-        geometries the general kernel (boundary terms read only at boundary cells); the norm is formed in the same pass."""
+    def stencil(self, op: DiffusionOperator, u, out, c0, cx, cy, cs, rin=None, cr=0.0, norm_out=None, norms_out=None):
+        """out = c0 u + cx rLx u + cy rLy u + cs rD S + cr rin; with ``norm_out`` (device scalar) also max |out|, with
+        ``norms_out`` (``nfield`` device values) max |out| of every field.  Full rectangles with one boundary condition per
+        side use the plan's own operator (no per-cell geometry arrays); other geometries the general kernel (boundary terms
+        read only at boundary cells); the norms are formed in the same pass."""
+        if norms_out is not None:
+            if op.rect is not None:
+                _hip.check(self.lib.qp_adi_rect_combine_norms(op.rect.handle, _ptr(u), _ptr(rin), _ptr(out), c0, cx, cy, cs,
+                                                              cr, _ptr(self._ws), _ptr(norms_out), self.stream),
+                           "qp_adi_rect_combine_norms")
+            else:
+                _hip.check(self.lib.qp_stencil_combine_norms(C.byref(op.desc), op.r, _ptr(u), _ptr(rin), _ptr(out), c0, cx,
+                                                             cy, cs, cr, _ptr(self._ws), _ptr(norms_out), self.stream),
+                           "qp_stencil_combine_norms")
+            return
         if op.rect is not None:
             _hip.check(self.lib.qp_adi_rect_combine(op.rect.handle, _ptr(u), _ptr(rin), _ptr(out), c0, cx, cy, cs, cr,
                                                     _ptr(self._ws) if norm_out is not None else 0, _ptr(norm_out),
@@ -701,8 +715,12 @@ class Engine:
         R = self.scratch("cn_R", n).view(op.nfield, self.ncell)
         res = self.scratch("cn_res", n).view(op.nfield, self.ncell)
         v = self.scratch("cn_v", n).view(op.nfield, self.ncell)
-        norms = self.scratch("cn_norms", 2)           # [max |R|, max |R - A v|], both read back in one transfer
-        self.stencil(op, u, R, 1.0, 1.0, 1.0, 2.0, norm_out=norms[0:1])
+        # [max |R_k|, max |(R - A v)_k|] of every plane k, read back in one transfer per look: the iteration is accepted
+        # plane by plane (`_cn_plane_error`) - energy planes differ by many decades, and maxima over the whole batch would
+        # never look at a plane far below the largest one
+        nf = op.nfield
+        norms = self.scratch("cn_norms", 2 * nf)[:2 * nf]
+        self.stencil(op, u, R, 1.0, 1.0, 1.0, 2.0, norms_out=norms[:nf])
         rho = self.cn_contraction_bound(op)
         # Full rectangles (commuting Lx, Ly): one cycle of Peaceman-Rachford iterations with Jordan's parameters on the
         # spectrum of I/2 - r D L_dir - 8 plane transfers per iteration against 13 of the preconditioned iteration below and
@@ -726,14 +744,12 @@ class Engine:
                        "qp_adi_rect_pr_cycle")
             # the check needs the NORM of the residual only (its plane is formed again by the polishing loop if the check
             # fails): no output plane
-            self.stencil(op, u, None, -1.0, 1.0, 1.0, 0.0, rin=R, cr=1.0, norm_out=norms[1:2])
-            scale, err = (float(x) for x in norms.cpu())
-            if not np.isfinite(err):
-                raise FloatingPointError("exact-CN iteration diverged (non-finite residual)")
-            if err <= rtol * scale:
+            self.stencil(op, u, None, -1.0, 1.0, 1.0, 0.0, rin=R, cr=1.0, norms_out=norms[nf:])
+            err = self._cn_plane_error(norms)
+            if err <= rtol:
                 if op._pr_hold > 0:
                     op._pr_hold -= 1
-                elif err <= rtol * scale / 30.0 and J > 2:
+                elif err <= rtol / 30.0 and J > 2:
                     op._pr_J = J - 1
                 return len(cycle)
             op._pr_J, op._pr_hold = min(J + 1, 24), op._pr_backoff
@@ -758,24 +774,22 @@ class Engine:
         first = its
         while True:
             look = its >= blind or its >= max_iter
-            self.stencil(op, v, res, -1.0, 1.0, 1.0, 0.0, rin=R, cr=1.0, norm_out=norms[1:2] if look else None)
+            self.stencil(op, v, res, -1.0, 1.0, 1.0, 0.0, rin=R, cr=1.0, norms_out=norms[nf:] if look else None)
             if look:
-                scale, err = (float(x) for x in norms.cpu())
-                if not np.isfinite(err):
-                    raise FloatingPointError("exact-CN iteration diverged (non-finite residual)")
-                if err <= rtol * scale:
+                err = self._cn_plane_error(norms)
+                if err <= rtol:
                     break
                 if its >= max_iter:
                     raise RuntimeError(
                         f"exact-CN iteration did not reach rtol={rtol:g} in {max_iter} iterations (residual "
-                        f"{err / max(scale, 1e-300):.3g}, estimated contraction factor {rho:.4f}); the step is too stiff "
+                        f"{err:.3g} of its plane, estimated contraction factor {rho:.4f}); the step is too stiff "
                         "(r D = dt D / (2 dx^2) very large) - reduce dt or use diffusion_scheme='adi'.")
             self._precondition(op, res)
             _hip.check(self.lib.qp_axpy(n, 1.0, _ptr(res), _ptr(v), self.stream), "qp_axpy")
             its += 1
         # next call: one iteration fewer runs blind when this one was already far below the tolerance at its first look
         done = its - first
-        op._cn_its = done - 1 if (its == blind and done > 0 and err <= 0.01 * rtol * scale) else done
+        op._cn_its = done - 1 if (its == blind and done > 0 and err <= 0.01 * rtol) else done
         u.copy_(v)
         return its
 
@@ -793,12 +807,10 @@ class Engine:
         its = 0
         while True:
             look = its >= blind or its >= max_iter
-            self.stencil(op, v, res, -1.0, 1.0, 1.0, 0.0, rin=R, cr=1.0, norm_out=norms[1:2] if look else None)
+            self.stencil(op, v, res, -1.0, 1.0, 1.0, 0.0, rin=R, cr=1.0, norms_out=norms[op.nfield:] if look else None)
             if look:
-                scale, err = (float(x) for x in norms.cpu())
-                if not np.isfinite(err):
-                    raise FloatingPointError("exact-CN iteration diverged (non-finite residual)")
-                if err <= rtol * scale:
+                err = self._cn_plane_error(norms)
+                if err <= rtol:
                     break
                 if err > 10.0 * best:
                     return -max(its, 1)
@@ -806,7 +818,7 @@ class Engine:
                 if its >= max_iter:
                     raise RuntimeError(
                         f"exact-CN (Chebyshev) iteration did not reach rtol={rtol:g} in {max_iter} iterations (residual "
-                        f"{err / max(scale, 1e-300):.3g}, contraction bound {rho:.6f}); reduce dt or use "
+                        f"{err:.3g} of its plane, contraction bound {rho:.6f}); reduce dt or use "
                         "diffusion_scheme='adi'.")
             self._precondition(op, res)
             if its == 0:
@@ -817,8 +829,26 @@ class Engine:
                 rk = rn
             _hip.check(self.lib.qp_cheb_update(n, c1, _ptr(res), c2, _ptr(d), _ptr(v), self.stream), "qp_cheb_update")
             its += 1
-        op._cn_cheb_its = its - 1 if (its == blind and its > 0 and err <= 0.01 * rtol * scale) else its
+        op._cn_cheb_its = its - 1 if (its == blind and its > 0 and err <= 0.01 * rtol) else its
         return its
+
+    @staticmethod
+    def _cn_plane_error(norms) -> float:
+        """max_k (max |res_k| / max |R_k|) from ``norms`` = [max |R_k| ..., max |res_k| ...] on the device (one transfer):
+        the residual of the exact-CN iteration relative to its own plane.  A plane whose right-hand side is zero must have
+        a zero residual (inf otherwise).  A residual below the smallest normal number (2.2e-308) counts as zero, whatever
+        the plane's own scale: a plane whose right-hand side lies below about 2.2e-308 / rtol (2e-295 at the default rtol)
+        is in effect not held to rtol - subnormal arithmetic cannot express that ratio.  A non-finite right-hand side or
+        residual raises."""
+        h = norms.tolist()      # plain floats: a look costs the transfer, not array arithmetic (one plane is the common case)
+        nf = len(h) // 2
+        worst = 0.0
+        for scale, err in zip(h[:nf], h[nf:]):
+            if not (math.isfinite(err) and math.isfinite(scale)):
+                raise FloatingPointError("exact-CN iteration diverged (non-finite right-hand side or residual)")
+            if err >= _TINY:
+                worst = max(worst, err / scale if scale > 0.0 else math.inf)
+        return worst
 
     def _absmax_into(self, a, out) -> None:
         _hip.check(self.lib.qp_absmax(_ptr(a), a.numel(), _ptr(self._ws), _ptr(out), self.stream), "qp_absmax")

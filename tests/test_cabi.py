@@ -93,6 +93,16 @@ def test_argument_validation_happens_before_any_launch(lib):
     assert lib.qp_stencil_combine(C.byref(g), 0.1, 0, 0, 0, 1.0, 0.0, 0.0, 0.0, 0.0, 0) == -1
     assert b"positive" in lib.qp_last_error()
     assert lib.qp_axpy(0, 1.0, 0, 0, 0) == -1
+    # the per-field norm entries: the norms are their purpose, so a NULL result pointer is refused
+    g = _hip.GridDesc.make(4, 4, 2, 8, 8, 8, 8, 8, 8, 0)
+    assert lib.qp_stencil_combine_norms(C.byref(g), 0.1, 8, 0, 16, 1.0, 0.0, 0.0, 0.0, 0.0, 8, 0, 0) == -1
+    assert b"norms_out" in lib.qp_last_error()
+    assert lib.qp_stencil_combine_norms(C.byref(g), 0.1, 8, 0, 16, 1.0, 0.0, 0.0, 0.0, 0.0, 0, 8, 0) == -1
+    assert b"workspace" in lib.qp_last_error()
+    assert lib.qp_adi_rect_combine_norms(None, 8, 0, 16, 1.0, 0.0, 0.0, 0.0, 0.0, 8, 0, 0) == -1
+    assert b"norms_out" in lib.qp_last_error()
+    assert lib.qp_adi_rect_combine_norms(None, 8, 0, 16, 1.0, 0.0, 0.0, 0.0, 0.0, 8, 8, 0) == -1
+    assert b"plan" in lib.qp_last_error()
     t = _hip.CollisionTables.make(4, 7, 2, 0, 0, 0, 0, 0, 0, 0)
     assert lib.qp_collision_step(C.byref(t), 0, 10, 0, 0, 0, 0, 1.0, 0.1, 1, 1, 1, 0) == -1
 
