@@ -191,6 +191,12 @@ typedef struct qp_collision_tables {
  * size does not have.  Sizes with a kernel of their own, ne <= 16, ne >= 51, gap classes and the double half-step call are
  * not affected by the flag. */
 #define QP_COLL_PAD_BINS 16u
+/* Wide bins (opt-in): where qp_collision_wide_available(ne, nw) is 1 (65 <= ne <= 128, nw <= 512) and QP_COLL_FORCE_GENERIC
+ * is not set, a one-wave-per-pixel kernel with TWO energy bins per lane runs instead of the generic kernel: ph_scratch may
+ * be NULL (the per-pixel phonon sums live in LDS), kr0 / ks0 / idx_diff / idx_sum must be symmetric and sign antisymmetric
+ * (as for the wave kernel), any class map.  Deterministic when diag_bin vouches for the bin-map structure, LDS atomics
+ * otherwise.  No fused Pauli guard; the double half-step call is not affected.  Sizes outside the query ignore the flag. */
+#define QP_COLL_WIDE_BINS 32u
 
 /*
  * One local coupled quasiparticle-phonon collision update of every interior cell
@@ -198,7 +204,7 @@ typedef struct qp_collision_tables {
  * are read as the OLD values; the new quasiparticle density goes to state_out (must not alias state_in),
  * phonons are updated in place when update_phonons != 0.
  * ph_scratch: the generic one-thread-per-cell kernel (ne > 64 or QP_COLL_FORCE_GENERIC) needs 2*nw*ncell doubles of
- * accumulators when phonons are updated; the register-resident kernels need 2*(merged bins)*ncell doubles only when
+ * accumulators when phonons are updated (not where QP_COLL_WIDE_BINS takes effect, see above); the register-resident kernels need 2*(merged bins)*ncell doubles only when
  * QP_COLL_SHARED_BINS is set and both processes update phonons (see diag_bin above); every other case takes NULL.
  * Cells whose flags lack QP_FLAG_ACTIVE are copied through unchanged.
  */
@@ -257,6 +263,9 @@ int qp_collision_member_tables_available(int32_t ne);
  * 32 for 31; 40 for 33-39; 50 for 41-49; 0 for every size with a one-pass or register kernel of its own, for ne <= 16 and
  * for ne >= 51. */
 int qp_collision_padded_ceiling(int32_t ne);
+/* 1 when the two-bins-per-lane wave kernel of QP_COLL_WIDE_BINS serves `ne` energy bins and `nw` phonon bins:
+ * 65 <= ne <= 128 and 1 <= nw <= 512. */
+int qp_collision_wide_available(int32_t ne, int32_t nw);
 
 /* The kernel family qp_collision_step (and the step inside the guarded calls) runs for these tables, cell count and
  * switches; have_scratch: whether ph_scratch would be non-NULL.  Launches nothing and reads only the struct itself (its
@@ -271,7 +280,8 @@ typedef enum qp_collision_route_kind {
   QP_ROUTE_WAVE = 5,             /* one wave per pixel */
   QP_ROUTE_GENERIC = 6,          /* one thread per cell, any table */
   QP_ROUTE_COPY = 7,             /* no effective process at a register-kernel size: n' = max(n, 0) */
-  QP_ROUTE_ONEPASS_PADDED        /* (8) one-pass kernel of the ceiling size on fewer live bins; only with QP_COLL_PAD_BINS */
+  QP_ROUTE_ONEPASS_PADDED,       /* (8) one-pass kernel of the ceiling size on fewer live bins; only with QP_COLL_PAD_BINS */
+  QP_ROUTE_WAVE_WIDE             /* (9) one wave per pixel, two energy bins per lane (65 <= ne <= 128); only with QP_COLL_WIDE_BINS */
 } qp_collision_route_kind;
 int qp_collision_route(const qp_collision_tables* t, int64_t ncell, int enable_recombination, int enable_scattering,
                        int update_phonons, int have_scratch);

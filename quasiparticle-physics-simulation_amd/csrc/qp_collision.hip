@@ -133,6 +133,11 @@ static bool onepass_enabled() {      // QPSIM_COLL_ONEPASS=0: the three-launch s
   return !e || atoi(e) != 0;
 }
 
+// QP_COLL_WIDE_BINS takes effect: the route needs no ph_scratch (validate_step_tables asks the same question)
+static bool wide_bins_ok(const qp_collision_tables& t) {
+  return (t.flags & QP_COLL_WIDE_BINS) && !(t.flags & QP_COLL_FORCE_GENERIC) && qp_collision_wide_available(t.ne, t.nw);
+}
+
 // The whole rule for which kernel family serves a single collision step, first match wins.
 Route collision_route(const qp_collision_tables& t, long ncell, bool en_r, bool en_s, bool upd, bool have_scratch) {
   const bool s = en_s && t.ks0, r = en_r && t.kr0;       // effective processes
@@ -179,6 +184,9 @@ Route collision_route(const qp_collision_tables& t, long ncell, bool en_r, bool 
   }
   // NE <= 64: one wave per pixel (any class map; LDS atomics unless the host vouched for the bin-map structure)
   if (!(t.flags & QP_COLL_FORCE_GENERIC) && t.ne <= 64 && t.nw <= 192) return QP_ROUTE_WAVE;
+  // wide bins (opt-in, QP_COLL_WIDE_BINS): 65 <= NE <= 128 with two energy bins per lane; without the flag, and outside the
+  // query's range, the generic kernel as ever
+  if (wide_bins_ok(t)) return QP_ROUTE_WAVE_WIDE;
   return QP_ROUTE_GENERIC;
 }
 
@@ -236,7 +244,7 @@ static int validate_step_tables(const qp_collision_tables* t, int64_t ncell, int
   QP_REQUIRE_AS(who, t->ne > 0 && t->nw > 0 && t->nclass > 0, "ne, nw, nclass must be positive");
   QP_REQUIRE_AS(who, t->idx_diff && t->idx_sum && t->sign, "idx maps / sign must be non-NULL");
   QP_REQUIRE_AS(who, t->nclass == 1 || t->cls, "cls is required when nclass > 1");
-  const bool no_scratch_ok = !(t->flags & QP_COLL_FORCE_GENERIC) && t->ne <= 64 && t->nw <= 192;
+  const bool no_scratch_ok = (!(t->flags & QP_COLL_FORCE_GENERIC) && t->ne <= 64 && t->nw <= 192) || qp::wide_bins_ok(*t);
   QP_REQUIRE_AS(who, !(upd && (en_r || en_s)) || have_scratch || no_scratch_ok,
                 "ph_scratch is required when phonons are updated by the generic kernel");
   QP_REQUIRE_AS(who, (t->diag_bin == nullptr) == (t->anti_bin == nullptr), "diag_bin and anti_bin come together");
@@ -282,6 +290,12 @@ static int collision_step_impl(const char* who, const qp_collision_tables* t, co
       const qp::WaveCollView wv{t->ne, t->nw, t->nclass, t->kr0, t->ks0, t->rho, t->idx_diff, t->idx_sum, t->sign, t->cls,
                                 t->diag_bin, t->anti_bin};
       qp::collision_wave_dispatch(wv, t->diag_bin != nullptr, c);
+      break;
+    }
+    case QP_ROUTE_WAVE_WIDE: {
+      const qp::WaveCollView wv{t->ne, t->nw, t->nclass, t->kr0, t->ks0, t->rho, t->idx_diff, t->idx_sum, t->sign, t->cls,
+                                t->diag_bin, t->anti_bin};
+      qp::collision_wave_wide_dispatch(wv, t->diag_bin != nullptr, c);
       break;
     }
     case QP_ROUTE_GENERIC: {    // the kernel tests the caller's switches itself (it also rewrites phonons with no table)
@@ -379,6 +393,9 @@ extern "C" int qp_collision_padded_ceiling(int32_t ne) {
   if (ne <= 16 || ne >= 50 || qp::collision_onepass_supported(ne) || qp::collision_fast_supported(ne)) return 0;
   return ne < 30 ? 30 : ne < 32 ? 32 : ne < 40 ? 40 : 50;
 }
+
+// The two-bins-per-lane wave kernel (QP_COLL_WIDE_BINS): lane l owns bins l and l + 64, and up to 8 phonon bins
+extern "C" int qp_collision_wide_available(int32_t ne, int32_t nw) { return ne >= 65 && ne <= 128 && nw >= 1 && nw <= 512; }
 
 // 1 when the gap-class variant (separable kernel tables, qp_collision_tables::gap_sq ...) exists as well
 extern "C" int qp_collision_register_kernel_classes(int32_t ne) { return qp::collision_fast_classes_supported(ne); }

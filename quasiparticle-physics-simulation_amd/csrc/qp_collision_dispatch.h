@@ -135,5 +135,6 @@ void collision_fast_dispatch(Route route, const qp_collision_tables& t, const Co
 void collision_onepass_dispatch(Route route, const qp_collision_tables& t, const CollCall& c);   // the two one-pass routes
 void collision_pair_dispatch(PairRoute route, const qp_collision_tables& t, const CollCall& c);
 void collision_wave_dispatch(const WaveCollView& v, bool structured, const CollCall& c);
+void collision_wave_wide_dispatch(const WaveCollView& v, bool structured, const CollCall& c);   // qp_collision_wave_wide.hip
 
 }  // namespace qp

@@ -51,8 +51,9 @@ class GenerationProgram(_SizedStructure):
 
 # qp_collision_route_kind: what qp_collision_route returns for tables it accepts
 (ROUTE_ONEPASS, ROUTE_REGISTER, ROUTE_REGISTER_MEMBERS, ROUTE_ONEPASS_CLASSES, ROUTE_REGISTER_CLASSES, ROUTE_WAVE,
- ROUTE_GENERIC, ROUTE_COPY, ROUTE_ONEPASS_PADDED) = range(9)
+ ROUTE_GENERIC, ROUTE_COPY, ROUTE_ONEPASS_PADDED, ROUTE_WAVE_WIDE) = range(10)
 COLL_PAD_BINS = 16      # QP_COLL_PAD_BINS of qp_collision_tables.flags
+COLL_WIDE_BINS = 32     # QP_COLL_WIDE_BINS
 
 
 class RectPlan(C.Structure):
@@ -142,6 +143,7 @@ SIGNATURES = {
     "qp_collision_onepass_available": (C.c_int, [C.c_int32]),
     "qp_collision_member_tables_available": (C.c_int, [C.c_int32]),
     "qp_collision_padded_ceiling": (C.c_int, [C.c_int32]),
+    "qp_collision_wide_available": (C.c_int, [C.c_int32, C.c_int32]),
     "qp_collision_pair_available": (C.c_int, [C.c_int32]),
     "qp_collision_route": (C.c_int, [C.POINTER(CollisionTables), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "qp_collision_double_step_guarded": (C.c_int, [C.POINTER(CollisionTables), c_dp, C.c_int64, c_dp, c_dp, c_dp, C.c_double,

@@ -94,7 +94,8 @@ class CollisionPlan:
     """What ``plan_collision_tables`` decided: the arrays to upload and the scalars of the handle.
 
     ``kernel`` is the family the table set can reach - "register" (the register, one-pass, member-table and gap-class
-    kernels), "wave" (one wave per pixel) or "generic" - not the kernel of a particular call.  With member tables a call
+    kernels), "wave" (one wave per pixel; with ``wide_bins`` at NE = 65 ... 128 its two-bins-per-lane form) or "generic" -
+    not the kernel of a particular call.  With member tables a call
     whose members are not wave-aligned (64 cells; one-pass sizes: block-aligned, 256) takes the class-map kernels;
     ``qp_collision_route`` answers for a particular call.  ``fast``: no phonon accumulator planes are needed; ``pair``:
     two consecutive half-steps can run as one pass (``qp_collision_double_step_guarded``)."""
@@ -118,7 +119,8 @@ class CollisionPlan:
 
 def plan_collision_tables(lib, ncell: int, mask_flat, kr0, ks0, rho, idx_diff, idx_sum, sign, cls_packed=None,
                           allow_fast=True, kernel: str = "auto", gap_params: dict | None = None, members: int = 1,
-                          member_classes: bool = False, pad_bins: bool = False) -> CollisionPlan:
+                          member_classes: bool = False, pad_bins: bool = False,
+                          wide_bins: bool = False) -> CollisionPlan:
     """Tables of ``Engine.make_collision_tables`` (which documents the arguments) for an engine of ``ncell`` cells with
     interior ``mask_flat``, on the host.  ``lib`` answers the ``qp_collision_*_available`` queries."""
     f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
@@ -200,6 +202,12 @@ def plan_collision_tables(lib, ncell: int, mask_flat, kr0, ks0, rho, idx_diff, i
     if padded:
         flag_bits |= 16
     wave_ok = ne <= 64 and nw <= 192
+    # wide bins (opt-in, QP_COLL_WIDE_BINS): NE = 65 ... 128 on the two-bins-per-lane wave kernel, any class map, no
+    # accumulator planes; every other size plans as without it
+    if (wide_bins and kernel in ("auto", "wave") and symmetric and not wave_ok
+            and bool(lib.qp_collision_wide_available(ne, nw))):
+        flag_bits |= 32
+        wave_ok = True
     label = ("generic" if (kernel == "generic" or not wave_ok) else
              "register" if padded or (kernel == "auto" and structure is not None
                                       and ((members_ok or members_onepass) if member_classes

@@ -860,7 +860,7 @@ class Engine:
     # -- collisions, generation, reductions -------------------------------------------------------------------
     def make_collision_tables(self, kr0, ks0, rho, idx_diff, idx_sum, sign, cls_packed=None, allow_fast=True,
                               kernel: str = "auto", gap_params: dict | None = None, members: int = 1,
-                              member_classes: bool = False, pad_bins: bool = False):
+                              member_classes: bool = False, pad_bins: bool = False, wide_bins: bool = False):
         """Upload per-gap-class tables ([C,NE,NE], [C,NE]) and maps; returns an opaque handle.
 
         ``kernel``: "auto" | "generic" | "wave" | "wave_unstructured" forces a collision kernel (tests, A/B timing).
@@ -876,12 +876,16 @@ class Engine:
         (``qp_collision_padded_ceiling(NE) != 0``) with structured symmetric maps and one class or member classes runs the
         one-pass kernel of the next instantiated size on its live bins; every array keeps the live size.  Sizes with their
         own kernel, NE >= 51 and gap classes plan exactly as without it.
+        ``wide_bins`` (opt-in, ``QP_COLL_WIDE_BINS``): NE = 65 ... 128 with at most 512 phonon bins and symmetric tables
+        (``qp_collision_wide_available``) runs the two-bins-per-lane wave kernel instead of the generic kernel, for one
+        class, gap classes and member classes alike: ``kernel == "wave"``, ``fast``, and no ``2 nw ncell`` accumulator
+        planes are allocated.  Every other size plans exactly as without it.
 
         Every rule is ``collision_tables.plan_collision_tables`` (host only); this method uploads its arrays and fills the
         struct.  ``handle["kernel"]`` is the family the table set can reach (``collision_tables.CollisionPlan``)."""
         plan = collision_tables.plan_collision_tables(self.lib, self.ncell, self.mask_flat, kr0, ks0, rho, idx_diff, idx_sum,
                                                       sign, cls_packed, allow_fast, kernel, gap_params, members,
-                                                      member_classes, pad_bins)
+                                                      member_classes, pad_bins, wide_bins)
         h = {name: None if a is None else self.torch.as_tensor(a, device=self.device) for name, a in plan.arrays.items()}
         h.update(ne=plan.ne, nclass=plan.nclass, nw=plan.nw, merged_slots=plan.merged_slots, symmetric=plan.symmetric,
                  member_classes=plan.member_classes, kernel=plan.kernel, fast=plan.fast, pair=plan.pair,

@@ -445,7 +445,8 @@ def _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, taus, 
     nw = omega_bins.size
     ctab, rho_tab = S._collision_tables(eng, E_bins, gap, precomputed if nonuniform else None, n, a["dynes_gamma"],
                                         tau_r_eff, tau_s_eff, a["T_c"], en_r, en_s, idx_diff, idx_sum, diff_sign, members=M,
-                                        member_params=tparams, member_ids=ids, pad_bins=a["collision_padded_bins"])
+                                        member_params=tparams, member_ids=ids, pad_bins=a["collision_padded_bins"],
+                                        wide_bins=a["collision_wide_bins"])
     phonon_host = np.stack([S._initial_phonon_state(mask, omega_bins, k["bath_temperature"], k["initial_condition_spec"])
                             for k in kws], axis=1).reshape(nw * M, n)
     state_host = np.stack([_prefixed(ids[m], S._initial_qp_state, mask, inits[m], E_bins, dE, gap, k["dynes_gamma"],

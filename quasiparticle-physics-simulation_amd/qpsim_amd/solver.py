@@ -23,6 +23,12 @@ and only crosses PCIe at store points.  Additive keyword arguments (all optional
     Sizes 51 ... 64, non-uniform gaps at any size and the double half-step pass (``num_energy_bins`` <= 16) are not
     affected; the default ``False`` runs exactly as before.  Results agree with the default to rounding (another
     summation order), not bit for bit.
+``collision_wide_bins``
+    ``True`` lets a ``num_energy_bins`` between 65 and 128 (at most 512 phonon bins) run a one-wave-per-pixel collision
+    kernel with two energy bins per lane instead of the generic one-thread-per-cell kernel (``QP_COLL_WIDE_BINS``): no
+    ``2 nw ncell`` accumulator planes are allocated, uniform and non-uniform gaps and ensemble sweeps alike.  Every other
+    size ignores it; the default ``False`` runs exactly as before.  Results agree with the default to rounding (another
+    summation order), not bit for bit.
 ``trace_out``, ``trace_regions``, ``trace_every``
     Time traces without stored frames: with a dict as ``trace_out`` the sums of every energy plane over up to 8 named
     regions (``trace_regions``: name -> boolean array of the mask's shape, regions may overlap; None: one region ``"all"``
@@ -495,12 +501,13 @@ def _initial_phonon_state(mask, omega_bins, bath_temperature, initial_condition_
 
 def _collision_tables(eng, E_bins, gap, nonuniform_pre, n, dynes_gamma, tau_r_eff, tau_s_eff, T_c, enable_recombination,
                       enable_scattering, idx_diff, idx_sum, diff_sign, members: int = 1, member_params=None,
-                      member_ids=None, pad_bins: bool = False):
+                      member_ids=None, pad_bins: bool = False, wide_bins: bool = False):
     """(device collision tables, rho per gap class) (solver.py:1189-1238); ``nonuniform_pre``: the precomputed arrays of a
     non-uniform gap (one class per distinct gap value), None for one gap.  ``member_params`` (ensemble parameter sweeps, one
     gap): ``(dynes_gamma, tau_r, tau_s, T_c)`` per member - one table set per member, each built exactly as that member's
     lone run builds its own, uploaded as member classes; the rho returned is then [members, NE].  ``pad_bins``
-    (``collision_padded_bins``) goes to the one-gap and the member-class tables; gap classes ignore it."""
+    (``collision_padded_bins``) goes to the one-gap and the member-class tables; gap classes ignore it.  ``wide_bins``
+    (``collision_wide_bins``) goes to all three."""
     if member_params is not None:
         built: dict = {}
         for j, key in enumerate(member_params):
@@ -517,7 +524,8 @@ def _collision_tables(eng, E_bins, gap, nonuniform_pre, n, dynes_gamma, tau_r_ef
         kr_tab = np.stack([built[key][1] for key in member_params]) if enable_recombination else None
         ks_tab = np.stack([built[key][2] for key in member_params]) if enable_scattering else None
         ctab = eng.make_collision_tables(kr_tab, ks_tab, rho_tab, idx_diff, idx_sum, diff_sign, None,
-                                         members=len(member_params), member_classes=True, pad_bins=pad_bins)
+                                         members=len(member_params), member_classes=True, pad_bins=pad_bins,
+                                         wide_bins=wide_bins)
         return ctab, rho_tab
     if nonuniform_pre is not None:
         gap_values = nonuniform_pre.get("gap_values")
@@ -532,7 +540,8 @@ def _collision_tables(eng, E_bins, gap, nonuniform_pre, n, dynes_gamma, tau_r_ef
               if enable_scattering else None)
     ctab = eng.make_collision_tables(kr_tab, ks_tab, rho_tab, idx_diff, idx_sum, diff_sign, cls,
                                      gap_params=dict(E=E_bins, gaps=class_gaps, tau_r=tau_r_eff, tau_s=tau_s_eff, T_c=T_c),
-                                     members=members, pad_bins=bool(pad_bins and nonuniform_pre is None))
+                                     members=members, pad_bins=bool(pad_bins and nonuniform_pre is None),
+                                     wide_bins=wide_bins)
     return ctab, rho_tab
 
 
@@ -642,6 +651,7 @@ def run_2d_crank_nicolson(
     cn_rtol: float = 1e-13,
     device=None,
     generation_on_device: bool = False,
+    collision_wide_bins: bool = False,
     collision_padded_bins: bool = False,
     trace_out: dict[str, Any] | None = None,
     trace_regions: dict[str, np.ndarray] | None = None,
@@ -711,7 +721,7 @@ def run_2d_crank_nicolson(
     phonon_host = _initial_phonon_state(mask, omega_bins, bath_temperature, initial_condition_spec)
     ctab, rho_tab = _collision_tables(eng, E_bins, gap, precomputed if nonuniform else None, n, dynes_gamma, tau_r_eff,
                                       tau_s_eff, T_c, enable_recombination, enable_scattering, idx_diff, idx_sum, diff_sign,
-                                      pad_bins=collision_padded_bins)
+                                      pad_bins=collision_padded_bins, wide_bins=collision_wide_bins)
 
     state_host = _initial_qp_state(mask, initial_field, E_bins, dE, gap, dynes_gamma, energy_weights,
                                    initial_condition_spec)
