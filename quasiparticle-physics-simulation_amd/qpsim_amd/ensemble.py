@@ -137,22 +137,16 @@ def generation_amounts(specs, t_start: float, dt_of_step: float) -> list:
     return [S._generation_amount(spec, t_start, dt_of_step) for spec in specs]
 
 
-def _bytes_per_member(kw: dict, traced: bool = False, coarse: bool = False) -> float:
-    """Device bytes one member needs: state planes (x2), phonon planes, diffusion / exact-CN work planes and, when time
-    traces (``traced``) or coarse frames (``coarse``) are taken, its share of their buffers."""
+def _bytes_per_member(kw: dict, plans=()) -> float:
+    """Device bytes one member needs: state planes (x2), phonon planes, diffusion / exact-CN work planes and its share of
+    the buffer of every sampler (``plans``: the time-trace / coarse-frame plans of the call), as the buffer check counts it."""
     mask = np.asarray(kw["mask"], dtype=bool)
     rows, cols = np.flatnonzero(mask.any(axis=1)), np.flatnonzero(mask.any(axis=0))
     ncell = (rows[-1] - rows[0] + 1) * (cols[-1] - cols[0] + 1) if rows.size else 1
     ne = int(kw["num_energy_bins"]) if kw["energy_gap"] > 0.0 else 1
     nw = 3 * ne
-    trace = 0.0
-    if traced:
-        regions = 1 if kw["trace_regions"] is None else len(kw["trace_regions"])
-        trace = 8.0 * Schedule(kw["total_time"], kw["dt"], 1, kw["trace_every"]).samples * regions * ne
-    if coarse:
-        cny, cnx = S.coarse_layout(mask, kw["coarse_bin"]).window[2:]
-        trace += 8.0 * Schedule(kw["total_time"], kw["dt"], 1, coarse_every=kw["coarse_every"]).coarse_samples * ne * cny * cnx
-    return 8.0 * ncell * (8 * ne + 3 * nw + 8) + trace
+    sched = Schedule(kw["total_time"], kw["dt"], 1)
+    return 8.0 * ncell * (8 * ne + 3 * nw + 8) + sum(S._sample_buffer_bytes(plan, sched, 1, ne) for plan in plans)
 
 
 def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = None, errors: str = "raise",
@@ -184,17 +178,16 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
     if errors not in ("raise", "return"):
         raise ValueError("errors must be 'raise' or 'return'")
     kws = member_arguments(list(members), common, sweep)
-    traces: dict | None = None if trace_out is None else {}
-    coarses: dict | None = None if coarse_out is None else {}
-    if trace_out is not None:
-        trace_out.clear()
-    if coarse_out is not None:
-        coarse_out.clear()
+    for sink in (trace_out, coarse_out):
+        if sink is not None:
+            sink.clear()
+    # per kind of sampler that is on (plan, sink of this call, {member: what its lone run's sink would receive})
+    sampling: list = []
     if kws:                        # refuse bad trace / coarse-frame arguments before any device is touched
-        S._trace_plan(np.asarray(kws[0]["mask"], dtype=bool), traces is not None, kws[0]["trace_regions"],
-                      kws[0]["trace_every"])
-        S._coarse_plan(np.asarray(kws[0]["mask"], dtype=bool), coarses is not None, kws[0]["coarse_bin"],
-                       kws[0]["coarse_every"])
+        a = kws[0]
+        sampling = [(plan, sink, {}) for plan, sink in S._sampling_plans(
+            np.asarray(a["mask"], dtype=bool), trace_out, a["trace_regions"], a["trace_every"], coarse_out, a["coarse_bin"],
+            a["coarse_every"])]
     _STATS.clear()
     _STATS.update(batches=0, pair_passes=0, guarded_calls=0)
     device_expr.reset_run_stats()
@@ -213,29 +206,25 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
         dev = kws[0].get("device")
         dev = torch.device("cuda", torch.cuda.current_device()) if (dev is None or world > 1) else torch.device(dev)
         free = float(torch.cuda.mem_get_info(dev)[0])
-    batches = plan_batches(mine, _bytes_per_member(kws[0], traces is not None, coarses is not None), free,
-                           max_members_per_batch)
+    batches = plan_batches(mine, _bytes_per_member(kws[0], [plan for plan, _, _ in sampling]), free, max_members_per_batch)
     # one batch on one process raises at once; otherwise every batch finishes and the earliest violation is raised after
     eager = errors == "raise" and world == 1 and len(batches) == 1
     results: dict[int, object] = {}
     for batch in batches:
         res = _run_batch([kws[m] for m in batch], batch, "raise" if eager else "return", None if world == 1 else dev,
-                         traces, coarses)
+                         sampling)
         results.update(zip(batch, res))
     out = [results.get(m) for m in range(len(kws))]
     if world > 1:
         import torch.distributed as dist
-        local = [(m, results[m], kws[m]["phonon_history_out"], None if traces is None else traces.get(m),
-                  None if coarses is None else coarses.get(m)) for m in mine]
+        local = [(m, results[m], kws[m]["phonon_history_out"], [got.get(m) for _, _, got in sampling]) for m in mine]
         gathered = [None] * world
         dist.all_gather_object(gathered, local, group=process_group)
         for part in gathered:
-            for m, res, ph, tr, co in part:
+            for m, res, ph, sampled in part:
                 out[m] = res
-                if traces is not None:
-                    traces[m] = tr
-                if coarses is not None:
-                    coarses[m] = co
+                for (_, _, got), value in zip(sampling, sampled):
+                    got[m] = value
                 target = kws[m]["phonon_history_out"]
                 if target is not None and ph is not None and target is not ph:
                     target.clear()
@@ -244,21 +233,18 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
         failures = [(getattr(r, "step", 0), m, r) for m, r in enumerate(out) if isinstance(r, Exception)]
         if failures:
             raise min(failures, key=lambda f: f[:2])[2]
-    if trace_out is not None:
-        trace_out.extend(traces.get(m) for m in range(len(kws)))
-    if coarse_out is not None:
-        coarse_out.extend(coarses.get(m) for m in range(len(kws)))
+    for _, sink, got in sampling:
+        sink.extend(got.get(m) for m in range(len(kws)))
     return out
 
 
-def _run_batch(kws: list[dict], ids: list[int], errors: str, device=None, traces: dict | None = None,
-               coarses: dict | None = None) -> list:
+def _run_batch(kws: list[dict], ids: list[int], errors: str, device=None, sampling=()) -> list:
     import torch
     dev = kws[0]["device"] if device is None else device
     dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
     with torch.cuda.device(dev):
         _STATS["batches"] += 1
-        return _run_batch_on_device(kws, ids, errors, dev, traces, coarses)
+        return _run_batch_on_device(kws, ids, errors, dev, sampling)
 
 
 def _prefixed(m: int, fn, *args):
@@ -268,9 +254,9 @@ def _prefixed(m: int, fn, *args):
         raise type(exc)(f"member {m}: {exc}") from exc
 
 
-def _run_batch_on_device(kws, ids, errors, device, traces=None, coarses=None):
-    """One batch; ``traces`` ({member id: trace dict}, None without time traces) receives what each member's ``trace_out``
-    would, ``coarses`` (None without coarse frames) what its ``coarse_out`` would."""
+def _run_batch_on_device(kws, ids, errors, device, sampling=()):
+    """One batch; the dict of every entry of ``sampling`` (per kind of sampler: plan, sink, {member id: dict}) receives
+    what each member's ``trace_out`` / ``coarse_out`` would, None for a member that failed."""
     a = kws[0]
     checked = [_prefixed(ids[j], S._checked_run_arguments, k["mask"], k["initial_field"], k["diffusion_coefficient"],
                          k["dt"], k["total_time"], k["store_every"], k["enable_diffusion"], k["enable_recombination"],
@@ -279,40 +265,30 @@ def _run_batch_on_device(kws, ids, errors, device, traces=None, coarses=None):
     mask, _, store_every, n, _, _ = checked[0]
     inits = [c[1] for c in checked]
     geom = S._run_geometry(mask, a["edges"], a["edge_conditions"], a["dx"], a["enable_diffusion"])
-    trace = S._trace_plan(mask, traces is not None, a["trace_regions"], a["trace_every"])
-    coarse = S._coarse_plan(mask, coarses is not None, a["coarse_bin"], a["coarse_every"])
-    sched = Schedule(a["total_time"], a["dt"], store_every, None if trace is None else trace.every,
-                     coarse_every=None if coarse is None else coarse.every)
+    sched = Schedule(a["total_time"], a["dt"], store_every)
     energy = a["energy_gap"] > 0.0
     nplanes = a["num_energy_bins"] if energy else 1
-    S._check_trace_buffer(trace, sched, len(kws), nplanes)
-    S._check_coarse_buffer(coarse, sched, len(kws), nplanes)
+    for plan, _, _ in sampling:
+        S._check_sample_buffer(plan, sched, len(kws), nplanes)
     eng = Engine(geom, device=device)
     eng.pin_stream()
     flags = eng.d_flags.reshape(-1).repeat(len(kws))     # [member][cell]
     out = Outputs(mask, a["dx"], [k["progress_callback"] for k in kws])
-    tracer = S._tracer(eng, mask, trace, sched, len(kws), nplanes)
-    coarser = S._coarse_frames(eng, coarse, sched, len(kws), nplanes)
+    samplers = tuple(plan.sampler(eng, mask, sched, len(kws), nplanes) for plan, _, _ in sampling)
     if not energy:
         results = S._run_scalar(eng, sched, out, inits, [k["diffusion_coefficient"] for k in kws], a["enable_diffusion"],
                                 [k["bath_temperature"] for k in kws], [k["phonon_history_out"] for k in kws],
-                                a["diffusion_scheme"], a["cn_rtol"], tracer, coarser)
+                                a["diffusion_scheme"], a["cn_rtol"], samplers)
     else:
         results = _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, [(c[4], c[5]) for c in checked],
-                                    tracer, coarser)
-    if tracer is not None or coarser is not None:
+                                    samplers)
+    if sampling:
         E_bins, dE = (S.build_energy_grid(a["energy_gap"], a["energy_min_factor"], a["energy_max_factor"], nplanes)
                       if energy else (None, None))
-    if coarser is not None:
-        sums = coarser.sums()
+    for (plan, _, got), sampler in zip(sampling, samplers):
+        rows = sampler.fetch()
         for j, res in enumerate(results):
-            coarses[ids[j]] = None if isinstance(res, Exception) else S._coarse_result(coarse, coarser.times, sums[:, j],
-                                                                                        E_bins, dE)
-    if tracer is not None:
-        density = tracer.density()
-        for j, res in enumerate(results):
-            traces[ids[j]] = None if isinstance(res, Exception) else S._trace_result(trace, tracer.times, density[:, j],
-                                                                                     E_bins, a["dx"], dE)
+            got[ids[j]] = None if isinstance(res, Exception) else plan.result(sampler.times, rows[:, j], E_bins, a["dx"], dE)
     return results
 
 
@@ -419,7 +395,7 @@ class _MembersRun(EnergyRun):
                 warnings.warn(f"member {self.ids[m]}: {warning}", stacklevel=8)
 
 
-def _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, taus, tracer=None, coarse=None):
+def _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, taus, samplers=()):
     """Energy-resolved mode for M members: the setup of ``run_2d_crank_nicolson`` over [bin][member][cell] planes."""
     a, M, mask = kws[0], len(kws), out.mask
     tau_s_eff, tau_r_eff = taus[0]
@@ -459,7 +435,7 @@ def _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, taus, 
     run.ctab, run.floor, run.physics = ctab, a["pauli_density_floor"], (en_r, en_s, not a["freeze_phonon_dynamics"])
     run.flags, run.generations = flags, [
         S._Generation(k["external_generation"], mask, E_bins, on_device=a["generation_on_device"]) for k in kws]
-    run.ids, run.errors, run.tracer, run.coarse = ids, errors, tracer, coarse
+    run.ids, run.errors, run.samplers = ids, errors, samplers
     run.verdict = S._guard_rule(eng, mask, E_bins, a["enforce_pauli"], a["pauli_warn_threshold"], a["pauli_error_threshold"])
     run.quiet_below = min([v for v in (a["pauli_warn_threshold"], a["pauli_error_threshold"]) if v is not None],
                           default=float("inf"))

@@ -74,7 +74,7 @@ from .models import (
 )
 from . import device_expr
 from .safe_eval import compile_safe_expression
-from .timeloop import CoarseFrames, EnergyRun, Outputs, Schedule, Tracer, energy_loop, scalar_loop
+from .timeloop import EnergyRun, Outputs, Sampler, Schedule, energy_loop, scalar_loop
 
 # names the reference exposes from qpsim.solver
 build_energy_grid = _tb.build_energy_grid
@@ -312,7 +312,14 @@ def _checked_run_arguments(mask, initial_field, diffusion_coefficient, dt, total
     return mask, initial_field, store_every, n, tau_s_eff, tau_r_eff
 
 
-TRACE_BUFFER_LIMIT = 256 << 20      # bytes of the device buffer of a time trace (samples x members x regions x planes x 8)
+# Time traces and coarse frames are the two kinds of sampler (timeloop.Sampler).  The checked arguments of each are a plan;
+# the two plan classes have the same methods, and everything below them handles a plan without knowing its kind:
+#   every                                        the cadence
+#   row_shape(nfield)                            the shape of one member's row of the device buffer
+#   sampler(eng, mask, sched, members, nfield)   the Sampler of a run on eng (whose grid is the bounding box of mask)
+#   result(times, rows, E_bins, dx, dE)          what the sink receives for one problem; rows [S, *row_shape] of that problem
+#   too_large(nbytes, rows, members, nfield)     the message for a buffer above the limit
+SAMPLE_BUFFER_LIMIT = 256 << 20     # bytes of the device buffer of one sampler (samples x members x row shape x 8)
 
 
 class _TracePlan:
@@ -321,6 +328,27 @@ class _TracePlan:
 
     def __init__(self, names, regions, cells, every):
         self.names, self.regions, self.cells, self.every = names, regions, cells, every
+
+    def row_shape(self, nfield: int) -> tuple:
+        return len(self.names), nfield
+
+    def sampler(self, eng, mask, sched: Schedule, members: int, nfield: int) -> Sampler:
+        offset = (int(np.flatnonzero(mask.any(axis=1))[0]), int(np.flatnonzero(mask.any(axis=0))[0]))
+        bits = eng.region_bits(self.regions, offset)
+        return Sampler(eng, sched, self.every, members, self.row_shape(nfield),
+                       lambda state, row: eng.region_sums(state, bits, members, row))
+
+    def result(self, times, density: np.ndarray, E_bins, dx: float, dE) -> dict:
+        """``density`` [S, R, planes]."""
+        density = np.ascontiguousarray(density)
+        number = dx * dx * (density[..., 0] if E_bins is None else dE * np.sum(density, axis=-1))
+        return {"times": list(times), "regions": list(self.names), "cells": list(self.cells),
+                "energy_bins": None if E_bins is None else np.array(E_bins, dtype=float), "density": density, "number": number}
+
+    def too_large(self, nbytes: int, rows: int, members: int, nfield: int) -> str:
+        return (f"trace_every={self.every} gives a trace buffer of {nbytes / 2 ** 20:.0f} MiB ({rows} samples x "
+                f"{members} members x {len(self.names)} regions x {nfield} planes x 8 B), above the limit of "
+                f"{SAMPLE_BUFFER_LIMIT >> 20} MiB; use a larger trace_every.")
 
 
 def _trace_plan(mask: np.ndarray, tracing: bool, trace_regions, trace_every):
@@ -347,40 +375,48 @@ def _trace_plan(mask: np.ndarray, tracing: bool, trace_regions, trace_every):
     return _TracePlan(names, regions, [int(np.sum(r & mask)) for r in regions], int(trace_every))
 
 
-def _check_trace_buffer(plan, sched: Schedule, members: int, nfield: int) -> None:
-    if plan is None:
-        return
-    nbytes = 8 * sched.samples * members * len(plan.names) * nfield
-    if nbytes > TRACE_BUFFER_LIMIT:
-        raise ValueError(f"trace_every={plan.every} gives a trace buffer of {nbytes / 2 ** 20:.0f} MiB ({sched.samples} samples x "
-                         f"{members} members x {len(plan.names)} regions x {nfield} planes x 8 B), above the limit of "
-                         f"{TRACE_BUFFER_LIMIT >> 20} MiB; use a larger trace_every.")
-
-
-def _tracer(eng, mask, plan, sched: Schedule, members: int, nfield: int):
-    """The ``Tracer`` of a run on ``eng`` (whose grid is the bounding box of ``mask``), None without a plan."""
-    if plan is None:
-        return None
-    offset = (int(np.flatnonzero(mask.any(axis=1))[0]), int(np.flatnonzero(mask.any(axis=0))[0]))
-    return Tracer(eng, eng.region_bits(plan.regions, offset), len(plan.names), members, nfield, sched.samples)
-
-
-def _trace_result(plan, times, density: np.ndarray, E_bins, dx: float, dE) -> dict:
-    """What ``trace_out`` receives for one problem; ``density`` [S, R, planes] of that problem."""
-    density = np.ascontiguousarray(density)
-    number = dx * dx * (density[..., 0] if E_bins is None else dE * np.sum(density, axis=-1))
-    return {"times": list(times), "regions": list(plan.names), "cells": list(plan.cells),
-            "energy_bins": None if E_bins is None else np.array(E_bins, dtype=float), "density": density, "number": number}
-
-
-COARSE_BUFFER_LIMIT = 256 << 20     # bytes of the device buffer of coarse frames (samples x members x planes x cny x cnx x 8)
-
-
 class _CoarsePlan:
     """Checked coarse-frame arguments of a run: ``bin``, ``every`` and the ``engine.CoarseLayout`` of the mask."""
 
     def __init__(self, bin, every, layout):
         self.bin, self.every, self.layout = bin, every, layout
+
+    def row_shape(self, nfield: int) -> tuple:
+        return (nfield,) + self.layout.window[2:]
+
+    def sampler(self, eng, mask, sched: Schedule, members: int, nfield: int) -> Sampler:
+        oy, ox = self.layout.offset
+        return Sampler(eng, sched, self.every, members, self.row_shape(nfield),
+                       lambda state, row: eng.block_sums(state, members, self.bin, oy, ox, row))
+
+    def result(self, times, sums: np.ndarray, E_bins, dx, dE) -> dict:
+        """``sums`` [S, planes, cny, cnx], as fetched.  The arrays of a long run are large, so each is formed in one pass: a
+        division by NaN marks the blocks without cells."""
+        lay = self.layout
+        wy, wx, cny, cnx = lay.window
+        if (cny, cnx) == lay.shape:
+            energy_sums = np.ascontiguousarray(sums)
+        else:
+            energy_sums = np.zeros(sums.shape[:2] + lay.shape)
+            energy_sums[:, :, wy:wy + cny, wx:wx + cnx] = sums
+        cells = np.where(lay.cells == 0, np.nan, lay.cells.astype(float))
+        energy_frames = energy_sums / cells
+        if E_bins is None:
+            frames = energy_frames[:, 0].copy()
+        else:
+            frames = np.sum(energy_sums, axis=1)
+            frames *= dE
+            frames /= cells
+        return {"times": list(times), "bin": self.bin, "cells": lay.cells.copy(),
+                "energy_bins": None if E_bins is None else np.array(E_bins, dtype=float), "energy_sums": energy_sums,
+                "energy_frames": energy_frames, "frames": frames}
+
+    def too_large(self, nbytes: int, rows: int, members: int, nfield: int) -> str:
+        cny, cnx = self.layout.window[2:]
+        return (f"coarse_every={self.every}, coarse_bin={self.bin} give a coarse-frame buffer of "
+                f"{nbytes / 2 ** 20:.0f} MiB ({rows} samples x {members} members x {nfield} planes x "
+                f"{cny} x {cnx} blocks x 8 B), above the limit of {SAMPLE_BUFFER_LIMIT >> 20} MiB; use a larger "
+                f"coarse_every or coarse_bin.")
 
 
 def _coarse_plan(mask: np.ndarray, wanted: bool, coarse_bin, coarse_every):
@@ -399,46 +435,33 @@ def _coarse_plan(mask: np.ndarray, wanted: bool, coarse_bin, coarse_every):
     return _CoarsePlan(int(coarse_bin), int(coarse_every), coarse_layout(mask, int(coarse_bin)))
 
 
-def _check_coarse_buffer(plan, sched: Schedule, members: int, nfield: int) -> None:
+def _sample_buffer_bytes(plan, sched: Schedule, members: int, nfield: int) -> int:
+    return 8 * sched.rows(plan.every) * members * int(np.prod(plan.row_shape(nfield)))
+
+
+def _check_sample_buffer(plan, sched: Schedule, members: int, nfield: int) -> None:
     if plan is None:
         return
-    cny, cnx = plan.layout.window[2:]
-    nbytes = 8 * sched.coarse_samples * members * nfield * cny * cnx
-    if nbytes > COARSE_BUFFER_LIMIT:
-        raise ValueError(f"coarse_every={plan.every}, coarse_bin={plan.bin} give a coarse-frame buffer of "
-                         f"{nbytes / 2 ** 20:.0f} MiB ({sched.coarse_samples} samples x {members} members x {nfield} planes x "
-                         f"{cny} x {cnx} blocks x 8 B), above the limit of {COARSE_BUFFER_LIMIT >> 20} MiB; use a larger "
-                         f"coarse_every or coarse_bin.")
+    nbytes = _sample_buffer_bytes(plan, sched, members, nfield)
+    if nbytes > SAMPLE_BUFFER_LIMIT:
+        raise ValueError(plan.too_large(nbytes, sched.rows(plan.every), members, nfield))
 
 
-def _coarse_frames(eng, plan, sched: Schedule, members: int, nfield: int):
-    """The ``CoarseFrames`` of a run on ``eng`` (whose grid is the bounding box of the mask), None without a plan."""
-    if plan is None:
-        return None
-    return CoarseFrames(eng, plan.bin, plan.layout.offset, members, nfield, sched.coarse_samples)
+def _sampling_plans(mask, trace_out, trace_regions, trace_every, coarse_out, coarse_bin, coarse_every) -> list:
+    """The active ``(plan, sink)`` pairs of a run, the trace before the coarse frames; all six arguments are checked before
+    a sink is cleared."""
+    kinds = ((_trace_plan(mask, trace_out is not None, trace_regions, trace_every), trace_out),
+             (_coarse_plan(mask, coarse_out is not None, coarse_bin, coarse_every), coarse_out))
+    active = [(plan, sink) for plan, sink in kinds if plan is not None]
+    for _, sink in active:
+        sink.clear()
+    return active
 
 
-def _coarse_result(plan, times, sums: np.ndarray, E_bins, dE) -> dict:
-    """What ``coarse_out`` receives for one problem; ``sums`` [S, planes, cny, cnx] of that problem, as fetched.  The arrays of
-    a long run are large, so each is formed in one pass: a division by NaN marks the blocks without cells."""
-    lay = plan.layout
-    wy, wx, cny, cnx = lay.window
-    if (cny, cnx) == lay.shape:
-        energy_sums = np.ascontiguousarray(sums)
-    else:
-        energy_sums = np.zeros(sums.shape[:2] + lay.shape)
-        energy_sums[:, :, wy:wy + cny, wx:wx + cnx] = sums
-    cells = np.where(lay.cells == 0, np.nan, lay.cells.astype(float))
-    energy_frames = energy_sums / cells
-    if E_bins is None:
-        frames = energy_frames[:, 0].copy()
-    else:
-        frames = np.sum(energy_sums, axis=1)
-        frames *= dE
-        frames /= cells
-    return {"times": list(times), "bin": plan.bin, "cells": lay.cells.copy(),
-            "energy_bins": None if E_bins is None else np.array(E_bins, dtype=float), "energy_sums": energy_sums,
-            "energy_frames": energy_frames, "frames": frames}
+def _deliver_samples(sampling, samplers, E_bins, dx, dE) -> None:
+    """Fills the sinks of a lone run (member 0 of its samplers) from ``sampling``, the pairs of ``_sampling_plans``."""
+    for (plan, sink), sampler in zip(sampling, samplers):
+        sink.update(plan.result(sampler.times, sampler.fetch()[:, 0], E_bins, dx, dE))
 
 
 def _run_geometry(mask, edges, edge_conditions, dx, enable_diffusion):
@@ -669,12 +692,7 @@ def run_2d_crank_nicolson(
     mask, initial_field, store_every, n, tau_s_eff, tau_r_eff = _checked_run_arguments(
         mask, initial_field, diffusion_coefficient, dt, total_time, store_every, enable_diffusion, enable_recombination,
         enable_scattering, tau_0, tau_s, tau_r, external_generation, phonon_history_out)
-    trace = _trace_plan(mask, trace_out is not None, trace_regions, trace_every)
-    coarse = _coarse_plan(mask, coarse_out is not None, coarse_bin, coarse_every)
-    if trace_out is not None:
-        trace_out.clear()
-    if coarse_out is not None:
-        coarse_out.clear()
+    sampling = _sampling_plans(mask, trace_out, trace_regions, trace_every, coarse_out, coarse_bin, coarse_every)
     device_expr.reset_run_stats()
 
     # Device grid = bounding box of the mask.  Interior cells keep their argwhere (row-major) order under the crop, so
@@ -682,24 +700,19 @@ def run_2d_crank_nicolson(
     # mask whose interior is a solid rectangle inside a padded frame (the reference's built-in geometry) thereby
     # becomes a full rectangle on the device and takes the tiled ADI path.
     geom = _run_geometry(mask, edges, edge_conditions, dx, enable_diffusion)
-    sched = Schedule(total_time, dt, store_every, None if trace is None else trace.every,
-                     coarse_every=None if coarse is None else coarse.every)
+    sched = Schedule(total_time, dt, store_every)
     nplanes = num_energy_bins if energy_gap > 0.0 else 1
-    _check_trace_buffer(trace, sched, 1, nplanes)
-    _check_coarse_buffer(coarse, sched, 1, nplanes)
+    for plan, _ in sampling:
+        _check_sample_buffer(plan, sched, 1, nplanes)
     eng = Engine(geom, device=device)
     eng.pin_stream()          # one stream for the whole run: skip the per-launch lookup
     out = Outputs(mask, dx, [progress_callback])
-    tracer = _tracer(eng, mask, trace, sched, 1, nplanes)
-    coarser = _coarse_frames(eng, coarse, sched, 1, nplanes)
+    samplers = tuple(plan.sampler(eng, mask, sched, 1, nplanes) for plan, _ in sampling)
 
     if not energy_gap > 0.0:
         result = _run_scalar(eng, sched, out, [initial_field], [diffusion_coefficient], enable_diffusion, [bath_temperature],
-                             [phonon_history_out], diffusion_scheme, cn_rtol, tracer, coarser)[0]
-        if tracer is not None:
-            trace_out.update(_trace_result(trace, tracer.times, tracer.density()[:, 0], None, dx, None))
-        if coarser is not None:
-            coarse_out.update(_coarse_result(coarse, coarser.times, coarser.sums()[:, 0], None, None))
+                             [phonon_history_out], diffusion_scheme, cn_rtol, samplers)[0]
+        _deliver_samples(sampling, samplers, None, dx, None)
         return result
 
     # ------------------------------------------------------------------ energy-resolved mode
@@ -732,7 +745,7 @@ def run_2d_crank_nicolson(
     run.physics = (enable_recombination, enable_scattering, not freeze_phonon_dynamics)
     run.generation = _Generation(external_generation, mask, E_bins, on_device=generation_on_device)
     run.verdict = _guard_rule(eng, mask, E_bins, enforce_pauli, pauli_warn_threshold, pauli_error_threshold)
-    run.tracer, run.coarse = tracer, coarser
+    run.samplers = samplers
 
     collisions = bool(enable_recombination or enable_scattering)
     energy_loop(run, sched, diffuser, collisions=collisions,
@@ -744,10 +757,7 @@ def run_2d_crank_nicolson(
     if phonon_history_out is not None:
         phonon_history_out.clear()
         phonon_history_out.update(_dynamic_phonon_history(out, 0, omega_bins))
-    if tracer is not None:
-        trace_out.update(_trace_result(trace, tracer.times, tracer.density()[:, 0], E_bins, dx, dE))
-    if coarser is not None:
-        coarse_out.update(_coarse_result(coarse, coarser.times, coarser.sums()[:, 0], E_bins, dE))
+    _deliver_samples(sampling, samplers, E_bins, dx, dE)
     return out.times, out.frames[0], out.mass[0], _color_limits(out.frames[0]), out.energy_frames[0], E_bins
 
 
@@ -910,10 +920,9 @@ def _dynamic_phonon_history(out: Outputs, m: int, omega_bins) -> dict:
 
 
 def _run_scalar(eng: Engine, sched, out: Outputs, inits, coefficients, enable_diffusion, bath_temperatures, histories,
-                scheme, rtol, tracer=None, coarse=None) -> list:
+                scheme, rtol, samplers=()) -> list:
     """Legacy scalar mode, energy_gap == 0 (solver.py:1517-1587), for M members as one [M, ncell] field set; the result
-    tuple of every member.  ``tracer`` / ``coarse``: the time traces / coarse frames of the M fields (one plane per member),
-    read by the caller."""
+    tuple of every member.  ``samplers``: the samplers of the M fields (one plane per member), fetched by the caller."""
     mask, M = out.mask, out.members
     u_host = np.stack([f[mask].astype(float) for f in inits])
     u = eng.upload_packed(u_host)
@@ -921,7 +930,7 @@ def _run_scalar(eng: Engine, sched, out: Outputs, inits, coefficients, enable_di
                 if enable_diffusion else None)
     out.add_host_frames(0.0, [reconstruct_field(mask, v) for v in u_host],
                         [float(np.sum(v) * out.dx * out.dx) for v in u_host])
-    scalar_loop(sched, diffuser, u, out, eng, tracer, coarse)
+    scalar_loop(sched, diffuser, u, out, eng, samplers)
     for T_bath, history in zip(bath_temperatures, histories):
         if history is not None:
             f, ef, bins, meta = build_fixed_phonon_history(mask=mask, times=out.times, bath_temperature=T_bath,

@@ -8,15 +8,15 @@ and opening half-step, the Pauli guard read ``guard_lag`` steps late, the short 
 the ``state`` / ``state_alt`` swap and the store point.  ``Outputs`` keeps the host-side results of M members; a lone run is
 M = 1.
 
-Time traces (opt-in): a ``Schedule`` with ``trace_every`` also names *sampled* steps, and a ``Tracer`` enqueues at each of
-them the region sums of every plane of the state into one row of a device buffer that is fetched once, after the loop.  A
-sampled step is sequenced exactly like a stored one (no pair pass across it, the stretch of diffusion steps ends there, the
-guard is read), so the state it sees is the state a run with ``store_every = trace_every`` stores there; it downloads no
-frame.  Without a tracer no step is sampled and both loops issue exactly the calls they issued before.
-
-Coarse frames (opt-in) work the same way one level up in size: a ``Schedule`` with ``coarse_every`` names its own sampled
-steps, and a ``CoarseFrames`` enqueues at each of them the b x b block sums of every plane into one row of its device buffer.
-A step sampled by either cadence is sequenced as above; each sampler is called at the steps of its own cadence only.
+Samplers (opt-in; time traces and coarse frames are the two kinds): a ``Sampler`` has a cadence ``every`` and a device
+buffer with one row per sample - t = 0, every ``every``-th step and the last (``Schedule.due`` / ``Schedule.rows``) - and at
+each of its steps enqueues one reduction of the state into the next row: the region sums of every plane for a trace, the
+b x b block sums of every plane for the coarse frames.  The buffer is fetched once, after the loop.  Both loops take a
+tuple of samplers.  A step that is due for any of them is sequenced exactly like a stored one (no pair pass across it, the
+stretch of diffusion steps ends there, the guard is read), so the state it sees is the state a run with ``store_every`` =
+that cadence stores there; it downloads no frame.  Each sampler is called at the steps of its own cadence only, those due
+at one step in the order of the tuple.  With an empty tuple no step is sampled and both loops issue exactly the calls they
+issued before.
 """
 from __future__ import annotations
 
@@ -34,40 +34,23 @@ def _step_plan(total_time: float, dt: float) -> tuple[int, float, int]:
 
 class Schedule:
     """Step sizes and store points of a run: ``full_steps`` steps of ``dt``, then one of ``rem`` if that is positive.
-    ``trace_every`` (None: no traces) adds the sampled steps of a time trace: every ``trace_every``-th and the last;
-    ``coarse_every`` (None: no coarse frames) in the same way those of the coarse frames."""
+    ``due`` / ``rows`` serve any cadence ``every`` (None: none) of sampled steps: every ``every``-th and the last."""
 
-    def __init__(self, total_time: float, dt: float, store_every: int, trace_every: int | None = None,
-                 coarse_every: int | None = None):
-        self.dt, self.store_every, self.trace_every, self.coarse_every = dt, store_every, trace_every, coarse_every
+    def __init__(self, total_time: float, dt: float, store_every: int):
+        self.dt, self.store_every = dt, store_every
         self.full_steps, self.rem, self.total_steps = _step_plan(total_time, dt)
 
     def stored(self, step: int) -> bool:
         return step % self.store_every == 0 or step == self.total_steps
 
-    def _on(self, every: int | None, step: int) -> bool:
+    def due(self, every: int | None, step: int) -> bool:
         return every is not None and (step % every == 0 or step == self.total_steps)
 
-    def _rows(self, every: int | None) -> int:
+    def rows(self, every: int | None) -> int:
+        """Samples of a cadence: t = 0 and every step that is due."""
         if every is None:
             return 0
         return 1 + self.total_steps // every + (1 if self.total_steps % every else 0)
-
-    def sampled(self, step: int) -> bool:
-        return self._on(self.trace_every, step)
-
-    def coarse_sampled(self, step: int) -> bool:
-        return self._on(self.coarse_every, step)
-
-    @property
-    def samples(self) -> int:
-        """Rows of a trace: t = 0 and every sampled step."""
-        return self._rows(self.trace_every)
-
-    @property
-    def coarse_samples(self) -> int:
-        """Coarse frames of a run: t = 0 and every step of the coarse cadence."""
-        return self._rows(self.coarse_every)
 
     def dt_of(self, step: int) -> float:
         return self.rem if step > self.full_steps else self.dt
@@ -168,71 +151,52 @@ class Outputs:
         self.lazy.add(ticket, lambda arr: [series[m].__setitem__(k, arr[m]) for m in range(self.members)])
 
 
-class Tracer:
-    """Time traces of M members: at every sample the sums of each plane [field][member][cell] over up to 8 regions
-    (``Engine.region_sums``) go into row k of a device buffer [samples, M, regions, fields]; nothing is read back before
-    ``density()``.  ``bits`` is the device plane of ``Engine.region_bits``."""
+class Sampler:
+    """One cadence of sampled steps over M members: at every sample ``reduce(state, out_row)`` enqueues one device
+    reduction of the planes [field][member][cell] into row k of a device buffer [rows, M, *row_shape]; nothing is read back
+    before ``fetch()``.  A time trace reduces with ``Engine.region_sums`` into rows (regions, fields), the coarse frames with
+    ``Engine.block_sums`` into rows (fields, cny, cnx)."""
 
-    def __init__(self, eng, bits, nregion: int, members: int, nfield: int, samples: int):
-        self.eng, self.bits, self.members = eng, bits, members
-        self.buffer = eng.empty(samples, members, nregion, nfield)
+    def __init__(self, eng, sched: Schedule, every: int, members: int, row_shape: tuple, reduce):
+        self.sched, self.every, self.reduce = sched, every, reduce
+        self.buffer = eng.empty(sched.rows(every), members, *row_shape)
         self.times: list[float] = []
 
+    def due(self, step: int) -> bool:
+        return self.sched.due(self.every, step)
+
     def sample(self, t: float, state) -> None:
-        self.eng.region_sums(state, self.bits, self.members, self.buffer[len(self.times)])
+        self.reduce(state, self.buffer[len(self.times)])
         self.times.append(float(t))
 
-    def density(self) -> np.ndarray:
-        """[samples taken, M, regions, fields] on the host (the one transfer of a trace)."""
+    def fetch(self) -> np.ndarray:
+        """[samples taken, M, *row_shape] on the host (the one transfer of a sampler)."""
         return self.buffer[:len(self.times)].cpu().numpy()
 
 
-class CoarseFrames:
-    """Coarse frames of M members: at every sample the sums of each plane [field][member][cell] over ``bin`` x ``bin`` blocks
-    (``Engine.block_sums``; ``offset`` = (oy, ox) of ``engine.coarse_layout``) go into row k of a device buffer
-    [samples, M, fields, cny, cnx]; nothing is read back before ``sums()``."""
-
-    def __init__(self, eng, bin: int, offset, members: int, nfield: int, samples: int):
-        self.eng, self.bin, self.offset, self.members = eng, int(bin), (int(offset[0]), int(offset[1])), members
-        cny, cnx = -(-(self.offset[0] + eng.ny) // self.bin), -(-(self.offset[1] + eng.nx) // self.bin)
-        self.buffer = eng.empty(samples, members, nfield, cny, cnx)
-        self.times: list[float] = []
-
-    def sample(self, t: float, state) -> None:
-        self.eng.block_sums(state, self.members, self.bin, self.offset[0], self.offset[1], self.buffer[len(self.times)])
-        self.times.append(float(t))
-
-    def sums(self) -> np.ndarray:
-        """[samples taken, M, fields, cny, cnx] on the host (the one transfer of the coarse frames)."""
-        return self.buffer[:len(self.times)].cpu().numpy()
+def _sample(samplers, t: float, state) -> None:
+    for sampler in samplers:
+        sampler.sample(t, state)
 
 
-def scalar_loop(sched: Schedule, diffuser, u, out: Outputs, eng, tracer: Tracer | None = None,
-                coarse: CoarseFrames | None = None) -> None:
-    """Legacy scalar mode, energy_gap == 0 (solver.py:1540-1555): nothing happens between two store points (or sampled
-    steps of ``tracer`` / ``coarse``) but diffusion steps, which ``diffuser.advance`` takes in one go."""
+def scalar_loop(sched: Schedule, diffuser, u, out: Outputs, eng, samplers=()) -> None:
+    """Legacy scalar mode, energy_gap == 0 (solver.py:1540-1555): nothing happens between two store points (or steps due
+    for one of ``samplers``) but diffusion steps, which ``diffuser.advance`` takes in one go."""
     t = 0.0
     done = 0
-    if tracer is not None:
-        tracer.sample(0.0, u)
-    if coarse is not None:
-        coarse.sample(0.0, u)
+    _sample(samplers, 0.0, u)
     for step in range(1, sched.total_steps + 1):
         t += sched.dt_of(step)                        # same accumulation order as the reference
         stored = sched.stored(step)
-        sampled = tracer is not None and sched.sampled(step)
-        coarsed = coarse is not None and sched.coarse_sampled(step)
-        if stored or sampled or coarsed:
+        due = [s for s in samplers if s.due(step)]
+        if stored or due:
             if diffuser is not None:
                 diffuser.advance(u, done + 1, step, sched.full_steps)
             done = step
         if stored:
             out.times.append(float(t))
             out.add_integrated(t, _device_frames_async(eng, u, out.mask))
-        if sampled:
-            tracer.sample(t, u)
-        if coarsed:
-            coarse.sample(t, u)
+        _sample(due, t, u)
     out.lazy.flush()
 
 
@@ -247,11 +211,9 @@ class EnergyRun:
     ``guard_launch()``                                 the guard of ``state`` on its own; its ticket
     ``guard_check(ticket, step, t)``                   reads a ticket; warns / raises with the step and time it belongs to
 
-    ``tracer``: the ``Tracer`` of the run, None (the default) without time traces; ``coarse``: its ``CoarseFrames``, None
-    (the default) without coarse frames.
+    ``samplers``: the ``Sampler`` s of the run, in the order they are called; empty (the default) without any.
     """
-    tracer: Tracer | None = None
-    coarse: CoarseFrames | None = None
+    samplers: tuple = ()
 
     def __init__(self, eng, out: Outputs, state, state_alt, phonon, dE: float, phonon_widths=None):
         self.eng, self.out = eng, out
@@ -289,10 +251,10 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
     ``pair_ok``: Strang steps that follow one another without a store point in between run the closing half-step of step k
     and the opening half-step of step k + 1 as ONE pass over the state (``run.collide_pair``); ``opened`` says that the
     generation term and the first half-step of the step now starting were already applied by that pass.
-    A sampled step of ``run.tracer`` or ``run.coarse`` ends a stretch exactly as a stored one does (``halt``) and enqueues
-    the region sums / block sums of the state instead of a download."""
+    A step that is due for one of ``run.samplers`` ends a stretch exactly as a stored one does (``halt``) and enqueues the
+    reductions of those samplers instead of a download."""
     pending: list = []
-    tracer, coarse = run.tracer, run.coarse
+    samplers = run.samplers
 
     def guard_flush(keep: int = 0) -> None:
         while len(pending) > keep:
@@ -312,10 +274,7 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
     pending.append((run.guard_launch(), 0, 0.0))
     guard_flush()
     run.store(0.0)
-    if tracer is not None:
-        tracer.sample(0.0, run.state)
-    if coarse is not None:
-        coarse.sample(0.0, run.state)
+    _sample(samplers, 0.0, run.state)
     times = run.out.times
     t = 0.0
     done = 0
@@ -324,9 +283,8 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
         final = step > sched.full_steps
         dt_step = sched.dt_of(step)
         stored = sched.stored(step)
-        sampled = tracer is not None and sched.sampled(step)
-        coarsed = coarse is not None and sched.coarse_sampled(step)
-        halt = stored or sampled or coarsed
+        due = [s for s in samplers if s.due(step)]
+        halt = stored or bool(due)
         if batch_diffusion:
             t += dt_step
             if halt:
@@ -335,10 +293,7 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
             if stored:
                 times.append(float(t))
                 run.store(t)
-            if sampled:
-                tracer.sample(t, run.state)
-            if coarsed:
-                coarse.sample(t, run.state)
+            _sample(due, t, run.state)
             continue
         if not opened:
             run.generate(t, dt_step)
@@ -369,9 +324,6 @@ def energy_loop(run: EnergyRun, sched: Schedule, diffuser, *, collisions: bool, 
         if stored:
             times.append(float(t))
             run.store(t)
-        if sampled:
-            tracer.sample(t, run.state)
-        if coarsed:
-            coarse.sample(t, run.state)
+        _sample(due, t, run.state)
     guard_flush()
     run.out.lazy.flush()

@@ -175,13 +175,14 @@ def test_a_buffer_above_the_limit_is_refused_before_a_device_is_needed():
 def test_the_buffer_limit_counts_samples_members_planes_and_blocks():
     mask = np.ones((1024, 1024), dtype=bool)
     plan = S._coarse_plan(mask, True, 8, 1)                            # 128 x 128 blocks
-    sched = Schedule(1.0, 1e-2, 1, coarse_every=1)                     # 101 samples
-    S._check_coarse_buffer(plan, sched, 1, 20)                         # 101 * 20 * 16384 * 8 B = 252.5 MiB
+    sched = Schedule(1.0, 1e-2, 1)
+    assert sched.rows(plan.every) == 101 and plan.row_shape(20) == (20, 128, 128)
+    S._check_sample_buffer(plan, sched, 1, 20)                         # 101 * 20 * 16384 * 8 B = 252.5 MiB
     with pytest.raises(ValueError, match="larger coarse_every or coarse_bin"):
-        S._check_coarse_buffer(plan, sched, 1, 21)                     # 265 MiB
+        S._check_sample_buffer(plan, sched, 1, 21)                     # 265 MiB
     with pytest.raises(ValueError, match="2 members"):
-        S._check_coarse_buffer(plan, sched, 2, 11)
-    S._check_coarse_buffer(None, Schedule(1.0, 1e-3, 1), 10 ** 6, 50)  # off: nothing to check
+        S._check_sample_buffer(plan, sched, 2, 11)
+    S._check_sample_buffer(None, Schedule(1.0, 1e-3, 1), 10 ** 6, 50)  # off: nothing to check
     assert S._coarse_plan(mask, False, 8, 1) is None
 
 
@@ -203,30 +204,29 @@ def test_coarse_keys_are_shared_by_all_members():
 def test_bytes_per_member_include_the_coarse_buffer():
     kw = ENS.member_arguments([{}], dict(_small(), energy_gap=180.0, num_energy_bins=8, coarse_every=3, coarse_bin=2))[0]
     # 4 samples, NE 8, 2 x 2 blocks on the 3 x 4 grid
-    assert ENS._bytes_per_member(kw, coarse=True) - ENS._bytes_per_member(kw) == 8 * 4 * 8 * 2 * 2
-    assert ENS._bytes_per_member(kw) == ENS._bytes_per_member(kw, traced=False, coarse=False)
+    plan = S._coarse_plan(kw["mask"], True, kw["coarse_bin"], kw["coarse_every"])
+    assert ENS._bytes_per_member(kw, [plan]) - ENS._bytes_per_member(kw) == 8 * 4 * 8 * 2 * 2
+    assert ENS._bytes_per_member(kw) == ENS._bytes_per_member(kw, [])
+    # the share is the figure the buffer check counts for one member, and both kinds add up
+    assert S._sample_buffer_bytes(plan, Schedule(kw["total_time"], kw["dt"], 1), 1, 8) == 8 * 4 * 8 * 2 * 2
+    trace = S._trace_plan(kw["mask"], True, None, 3)
+    assert ENS._bytes_per_member(kw, [trace, plan]) - ENS._bytes_per_member(kw) == 8 * 4 * 8 * (1 + 2 * 2)
 
 
 # ------------------------------------------------------------------------------------------------ schedule
 def test_the_two_cadences_of_a_schedule():
     steps = range(1, 24)
-    both = Schedule(2.25, 0.1, 100, 5, coarse_every=4)          # 22 steps of 0.1 and one of 0.05
-    assert both.total_steps == 23 and both.rem > 0.0
-    assert [k for k in steps if both.sampled(k)] == [5, 10, 15, 20, 23] and both.samples == 6
-    assert [k for k in steps if both.coarse_sampled(k)] == [4, 8, 12, 16, 20, 23] and both.coarse_samples == 7
-    assert [k for k in steps if both.stored(k)] == [23]
-    trace_only = Schedule(2.25, 0.1, 100, 5)
-    assert [k for k in steps if trace_only.sampled(k)] == [5, 10, 15, 20, 23] and trace_only.samples == 6
-    assert trace_only.coarse_samples == 0 and not any(trace_only.coarse_sampled(k) for k in steps)
-    coarse_only = Schedule(2.25, 0.1, 100, coarse_every=4)
-    assert [k for k in steps if coarse_only.coarse_sampled(k)] == [4, 8, 12, 16, 20, 23] and coarse_only.coarse_samples == 7
-    assert coarse_only.samples == 0 and not any(coarse_only.sampled(k) for k in steps)
+    sched = Schedule(2.25, 0.1, 100)                            # 22 steps of 0.1 and one of 0.05
+    assert sched.total_steps == 23 and sched.rem > 0.0
+    assert [k for k in steps if sched.due(5, k)] == [5, 10, 15, 20, 23] and sched.rows(5) == 6
+    assert [k for k in steps if sched.due(4, k)] == [4, 8, 12, 16, 20, 23] and sched.rows(4) == 7
+    assert [k for k in steps if sched.stored(k)] == [23]
+    # a cadence that is off has no row and no step, whatever the other one is
+    assert sched.rows(None) == 0 and not any(sched.due(None, k) for k in steps)
     off = Schedule(2.25, 0.1, 3)
-    assert off.samples == 0 and off.coarse_samples == 0
-    assert not any(off.sampled(k) or off.coarse_sampled(k) for k in steps)
+    assert off.rows(None) == 0 and not any(off.due(None, k) for k in steps)
     # the last step is sampled once when the cadence divides the step count
-    assert Schedule(0.8, 0.1, 1, coarse_every=4).coarse_samples == 3 and Schedule(0.8, 0.1, 1, coarse_every=1).coarse_samples == 9
-    assert Schedule(0.8, 0.1, 1, 4).samples == 3                # positional trace cadence as before
+    assert Schedule(0.8, 0.1, 1).rows(4) == 3 and Schedule(0.8, 0.1, 1).rows(1) == 9
 
 
 # ------------------------------------------------------------------------------------------------ sequencing
@@ -362,7 +362,7 @@ def test_a_coarse_step_is_sequenced_like_a_stored_one_and_sums_the_state_stored_
 
 
 def test_the_result_embeds_the_window_and_marks_blocks_without_cells():
-    """``_coarse_result`` on a 40 x 48 frame whose mask starts at (5, 9) and has a 16 x 16 hole, b = 8: the device sums land
+    """``_CoarsePlan.result`` on a 40 x 48 frame whose mask starts at (5, 9) and has a 16 x 16 hole, b = 8: the device sums land
     in their window of the full coarse frame with their bits, 0.0 around it, NaN means exactly where ``cells == 0``."""
     mask = np.zeros((40, 48), dtype=bool)
     mask[5:38, 9:47] = True
@@ -373,7 +373,7 @@ def test_the_result_embeds_the_window_and_marks_blocks_without_cells():
     rng = np.random.default_rng(2)
     sums = rng.random((3, 4, 5, 5)) * (lay.cells[:, 1:] > 0)
     E_bins, dE = np.linspace(180.0, 540.0, 4), 120.0
-    got = S._coarse_result(plan, [0.0, 0.1, 0.2], sums, E_bins, dE)
+    got = plan.result([0.0, 0.1, 0.2], sums, E_bins, 1.0, dE)
     assert got["energy_sums"].shape == (3, 4, 5, 6) and got["energy_sums"][..., 1:].tobytes() == sums.tobytes()
     assert np.all(got["energy_sums"][..., 0] == 0.0) and not np.signbit(got["energy_sums"]).any()
     empty = lay.cells == 0
@@ -384,7 +384,7 @@ def test_the_result_embeds_the_window_and_marks_blocks_without_cells():
         assert np.array_equal(got["energy_frames"][..., ~empty], (got["energy_sums"] / lay.cells)[..., ~empty])
         np.testing.assert_allclose(got["frames"][:, ~empty], (dE * got["energy_sums"].sum(axis=1) / lay.cells)[:, ~empty],
                                    rtol=1e-15)
-        scalar = S._coarse_result(plan, [0.0], sums[:1, :1], None, None)
+        scalar = plan.result([0.0], sums[:1, :1], None, 1.0, None)
         assert scalar["energy_bins"] is None
         assert np.array_equal(scalar["frames"], scalar["energy_frames"][:, 0], equal_nan=True)
         assert np.array_equal(scalar["frames"][:, ~empty], (scalar["energy_sums"][:, 0] / lay.cells)[:, ~empty])

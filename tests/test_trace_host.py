@@ -104,11 +104,12 @@ def test_bad_trace_arguments_are_refused_before_a_device_is_needed(kw, match):
 
 def test_the_buffer_limit_counts_members_regions_planes_and_samples():
     plan = S._trace_plan(np.ones((3, 4), dtype=bool), True, None, 1)
-    sched = Schedule(1.0, 1e-3, 1, 1)                                 # 1001 samples
-    S._check_trace_buffer(plan, sched, 640, 50)                       # 1001 * 640 * 1 * 50 * 8 B = 244 MiB
+    sched = Schedule(1.0, 1e-3, 1)
+    assert sched.rows(plan.every) == 1001 and plan.row_shape(50) == (1, 50)
+    S._check_sample_buffer(plan, sched, 640, 50)                      # 1001 * 640 * 1 * 50 * 8 B = 244 MiB
     with pytest.raises(ValueError, match="larger trace_every"):
-        S._check_trace_buffer(plan, sched, 700, 50)                   # 267 MiB
-    S._check_trace_buffer(None, Schedule(1.0, 1e-3, 1), 10 ** 6, 50)  # off: nothing to check
+        S._check_sample_buffer(plan, sched, 700, 50)                  # 267 MiB
+    S._check_sample_buffer(None, sched, 10 ** 6, 50)                  # off: nothing to check
 
 
 def test_trace_keys_are_shared_by_all_members():
@@ -127,20 +128,22 @@ def test_trace_keys_are_shared_by_all_members():
 def test_bytes_per_member_include_the_trace_buffer():
     kw = ENS.member_arguments([{}], dict(_small(), energy_gap=180.0, num_energy_bins=8, trace_every=3,
                                          trace_regions={"a": np.ones((3, 4), dtype=bool), "b": np.zeros((3, 4), dtype=bool)}))[0]
-    assert ENS._bytes_per_member(kw, traced=True) - ENS._bytes_per_member(kw) == 8 * 4 * 2 * 8   # 4 samples, 2 regions, NE 8
-    assert ENS._bytes_per_member(kw) == ENS._bytes_per_member(kw, traced=False)
+    plan = S._trace_plan(kw["mask"], True, kw["trace_regions"], kw["trace_every"])
+    assert ENS._bytes_per_member(kw, [plan]) - ENS._bytes_per_member(kw) == 8 * 4 * 2 * 8   # 4 samples, 2 regions, NE 8
+    assert ENS._bytes_per_member(kw) == ENS._bytes_per_member(kw, [])
+    # the share is the figure the buffer check counts for one member
+    assert S._sample_buffer_bytes(plan, Schedule(kw["total_time"], kw["dt"], 1), 1, 8) == 8 * 4 * 2 * 8
 
 
 # ------------------------------------------------------------------------------------------------ schedule
 def test_sample_schedule_with_a_remainder_step():
-    sched = Schedule(0.75, 0.1, 100, 3)                    # 7 steps of 0.1 and one of 0.05
+    sched = Schedule(0.75, 0.1, 100)                       # 7 steps of 0.1 and one of 0.05
     assert sched.total_steps == 8 and sched.rem > 0.0
-    assert [k for k in range(1, 9) if sched.sampled(k)] == [3, 6, 8]
-    assert sched.samples == 4                              # with t = 0
+    assert [k for k in range(1, 9) if sched.due(3, k)] == [3, 6, 8]
+    assert sched.rows(3) == 4                              # with t = 0
     assert [k for k in range(1, 9) if sched.stored(k)] == [8]
-    off = Schedule(0.75, 0.1, 3)
-    assert off.samples == 0 and not any(off.sampled(k) for k in range(1, 9))
-    assert Schedule(0.8, 0.1, 1, 4).samples == 3 and Schedule(0.8, 0.1, 1, 1).samples == 9
+    assert sched.rows(None) == 0 and not any(sched.due(None, k) for k in range(1, 9))      # no cadence
+    assert Schedule(0.8, 0.1, 1).rows(4) == 3 and Schedule(0.8, 0.1, 1).rows(1) == 9
 
 
 @pytest.mark.parametrize("name", ["full_adi_constant_pair", "scalar_adi", "diffusion_only_one_call"])
