@@ -434,6 +434,42 @@ int qp_region_sums(const double* state, const uint8_t* region_bits, int32_t nfie
                    int32_t nregion, void* workspace, double* out, void* stream);
 
 /*
+ * Collision rate traces (no reference counterpart on its time loop; the terms are those of solver.py:719-743).  Per cell
+ * and energy bin i, with q = rho * max(1 - n / max(rho, 1e-30), 0) and N the phonon occupation of the pair's bin, four
+ * non-negative channels in units of dn_i/dt:
+ *   0 scattering_in    dE q_i sum_j Ks_eff[j][i] n_j        Ks_eff[a][b] = ks0[a][b] (1 + N_|a-b|) where E_a > E_b,
+ *   1 scattering_out   n_i dE sum_j Ks_eff[i][j] q_j                       ks0[a][b] N_|a-b| where E_a < E_b, 0 where a == b
+ *   2 recombination    n_i 2 dE sum_j kr0[i][j] (1 + N_{i+j}) n_j
+ *   3 pair_breaking    2 dE q_i sum_j kr0[i][j] N_{i+j} q_j
+ * out[m][r][ch][i] = sum of channel ch over the cells c of member m with bit r of region_bits[c] set (region_bits as in
+ * qp_region_sums: one byte per cell of ONE member grid, holes carry no bit, so no flags plane is read).  Every entry of
+ * out[members][nregion][4][ne] is written; the channels of a disabled process (or of a NULL kr0 / ks0) and a region without
+ * cells are exactly 0.0.  state[ne][members * ncell_member] and phonon[nw][members * ncell_member] are only read, and not at
+ * all in a group of 8 cells without a region bit: NaN outside every region reaches no sum, and such a group costs its wave
+ * nothing (a call lasts as long as its busiest wave: DESIGN 6f).  Of the tables the call reads kr0, ks0, rho, idx_diff, idx_sum, sign and cls / nclass (cls covers all members *
+ * ncell_member cells, as in the collision calls; with QP_COLL_MEMBER_CLASSES class k owns the cells of its members, which
+ * cls says too); kr0 / ks0 / idx_diff / idx_sum must be symmetric and sign antisymmetric (row j serves the pairs (lane, j),
+ * as in the one-wave-per-pixel kernel; the caller checks).  The route flags and the one-pass images are ignored.
+ * Association: each sum runs over j = 0 ... ne-1 in order as fma(K * factor, x_j, sum) with factor 1 + N or N; the
+ * prefactors are (dE q_i) sum, (n_i dE) sum, (n_i (2 dE)) sum, ((2 dE) q_i) sum.
+ * Two launches, no atomics: a block of 4 waves owns one (chunk, member), a chunk being QP_RATES_CHUNK = 1024 consecutive
+ * cells of a member grid; wave w owns cells [256 w, 256 w + 256) of the chunk and walks them in groups of 8 in index order,
+ * lane <-> energy bin; the waves combine through LDS in wave order ((w0 + w1) + w2) + w3; the block writes nregion * 4 * ne
+ * partials; the second launch adds the partials of each (member, region, channel, bin) in chunk order.  Which lane adds
+ * which cell in which order depends on (ne, ncell_member, members, nregion) alone: equal inputs give bitwise equal
+ * outputs, and member m of a batch gives the bits of a lone call on its planes whatever the parity of ncell_member.
+ * workspace: qp_collision_rates_workspace_bytes = members * ceil(ncell_member / 1024) * nregion * 4 * ne * 8 bytes (0 for
+ * sizes the call refuses).  QP_ERR_UNSUPPORTED where qp_collision_rates_available(ne, nw) is 0 (it is 1 for 2 <= ne <= 64
+ * and 1 <= nw <= 191, and answers without a GPU) or nregion is outside 1 ... 8.
+ */
+#define QP_RATES_CHUNK 1024
+int qp_collision_rates_available(int32_t ne, int32_t nw);
+size_t qp_collision_rates_workspace_bytes(int32_t ne, int64_t ncell_member, int64_t members, int32_t nregion);
+int qp_collision_rates(const qp_collision_tables* t, const uint8_t* region_bits, int64_t ncell_member, int64_t members,
+                       int32_t nregion, const double* state, const double* phonon, double dE, int enable_recombination,
+                       int enable_scattering, void* workspace, double* out, void* stream);
+
+/*
  * Block sums (coarse frames; stands in for the frame stores of solver.py:1479-1494, reduced over bin x bin blocks).
  * state[nfield][members][ny * nx] is the layout of the time loop, flags[ny * nx] the flag plane of ONE member grid (only
  * QP_FLAG_ACTIVE is read).  bin = 2, 4, 8, 16, 32 or 64 is the block edge; blocks are aligned to the origin of the full

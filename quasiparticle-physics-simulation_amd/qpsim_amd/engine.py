@@ -1196,6 +1196,24 @@ class Engine:
         _hip.check(self.lib.qp_region_sums(_ptr(state), _ptr(bits), nfield, self.ncell, members, nregion, _ptr(ws),
                                            _ptr(out_row), self.stream), "qp_region_sums")
 
+    def collision_rates(self, tables, state, phonon, bits, members: int, dE: float, en_r, en_s, out_row) -> None:
+        """out_row[m][r][ch][i] = sum over the cells of region r of channel ch (scattering in / out, recombination, pair
+        breaking) of bin i (``qp_collision_rates``), ``state`` [NE][member][cell] and ``phonon`` [NW][member][cell] only
+        read, ``out_row`` one [members, regions, 4, NE] row of a caller-owned device buffer.  Enqueues two kernels and
+        nothing else.  The kernel reads row j of the tables for the pairs (lane, j): tables that are not symmetric are
+        refused here, on the host."""
+        members, nregion, ne = int(members), int(out_row.shape[-3]), int(tables["ne"])
+        if not tables["symmetric"]:
+            raise ValueError("collision_rates: kr0 / ks0 / idx_diff / idx_sum must be symmetric and sign antisymmetric")
+        if (state.numel() != ne * members * self.ncell or phonon.numel() != int(tables["nw"]) * members * self.ncell
+                or tuple(out_row.shape[-2:]) != (4, ne) or not out_row.is_contiguous()):
+            raise ValueError("collision_rates: out_row must be a contiguous [members, regions, 4, NE] row matching the state")
+        nbytes = int(self.lib.qp_collision_rates_workspace_bytes(ne, self.ncell, members, nregion))
+        ws = self.scratch("collision_rates", max((nbytes + 7) // 8, 1))
+        _hip.check(self.lib.qp_collision_rates(C.byref(tables["struct"]), _ptr(bits), self.ncell, members, nregion,
+                                               _ptr(state), _ptr(phonon), float(dE), int(bool(en_r)), int(bool(en_s)),
+                                               _ptr(ws), _ptr(out_row), self.stream), "qp_collision_rates")
+
     def block_sums(self, state, members: int, bin: int, oy: int, ox: int, out_row) -> None:
         """out_row[m][f][cy][cx] = sum of state[f][m][cell] over the active cells of one ``bin`` x ``bin`` block
         (``qp_block_sums``; ``(oy, ox)`` as ``coarse_layout`` gives them), ``state`` laid out [field][member][cell] and

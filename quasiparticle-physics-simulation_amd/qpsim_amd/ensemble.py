@@ -28,6 +28,10 @@ starts on an odd element, pairs its cells differently, and the sums agree to rou
 Coarse frames (``coarse_out=[]`` of the ensemble call, ``coarse_bin`` / ``coarse_every`` in the common arguments): one block
 reduction launch per sample serves all members of a batch.  A member's coarse frames are bit-equal to its lone run's
 wherever its state is (the conditions above), whatever the parity of the cell count.
+
+Collision rate traces (``rates_out=[]`` of the ensemble call, ``rates_regions`` / ``rates_every`` in the common arguments):
+one ``qp_collision_rates`` call per sample serves all members of a batch, with a sweep every member through its own tables.
+A member's rates are bit-equal to its lone run's wherever its state and phonons are, whatever the parity of the cell count.
 """
 from __future__ import annotations
 
@@ -151,7 +155,8 @@ def _bytes_per_member(kw: dict, plans=()) -> float:
 
 def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = None, errors: str = "raise",
                                    max_members_per_batch: int | None = None, process_group=None,
-                                   trace_out: list | None = None, coarse_out: list | None = None, **common) -> list:
+                                   trace_out: list | None = None, coarse_out: list | None = None,
+                                   rates_out: list | None = None, **common) -> list:
     """Run ``len(members)`` independent problems batched on the device.
 
     ``common`` takes the keyword arguments of ``run_2d_crank_nicolson``; ``members[m]`` overrides only the keys of
@@ -174,11 +179,14 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
     serves all members of a batch.
     Coarse frames: ``coarse_bin`` / ``coarse_every`` are shared keys of ``common`` and the sink is the list ``coarse_out`` of
     this call, handled exactly as ``trace_out`` is (one dict per member as the lone call fills its ``coarse_out``, None for
-    a failed member); one block reduction launch per sample serves all members of a batch."""
+    a failed member); one block reduction launch per sample serves all members of a batch.
+    Collision rate traces: ``rates_regions`` / ``rates_every`` are shared keys of ``common`` and the sink is the list
+    ``rates_out`` of this call, handled exactly as ``trace_out`` is; one ``qp_collision_rates`` call per sample serves all
+    members of a batch, with a sweep each member through its own tables."""
     if errors not in ("raise", "return"):
         raise ValueError("errors must be 'raise' or 'return'")
     kws = member_arguments(list(members), common, sweep)
-    for sink in (trace_out, coarse_out):
+    for sink in (trace_out, coarse_out, rates_out):
         if sink is not None:
             sink.clear()
     # per kind of sampler that is on (plan, sink of this call, {member: what its lone run's sink would receive})
@@ -187,7 +195,7 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
         a = kws[0]
         sampling = [(plan, sink, {}) for plan, sink in S._sampling_plans(
             np.asarray(a["mask"], dtype=bool), trace_out, a["trace_regions"], a["trace_every"], coarse_out, a["coarse_bin"],
-            a["coarse_every"])]
+            a["coarse_every"], rates_out, a["rates_regions"], a["rates_every"], a)]
     _STATS.clear()
     _STATS.update(batches=0, pair_passes=0, guarded_calls=0)
     device_expr.reset_run_stats()
@@ -436,6 +444,7 @@ def _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, taus, 
     run.flags, run.generations = flags, [
         S._Generation(k["external_generation"], mask, E_bins, on_device=a["generation_on_device"]) for k in kws]
     run.ids, run.errors, run.samplers = ids, errors, samplers
+    S._bind_rates(samplers, run)
     run.verdict = S._guard_rule(eng, mask, E_bins, a["enforce_pauli"], a["pauli_warn_threshold"], a["pauli_error_threshold"])
     run.quiet_below = min([v for v in (a["pauli_warn_threshold"], a["pauli_error_threshold"]) if v is not None],
                           default=float("inf"))

@@ -51,6 +51,18 @@ and only crosses PCIe at store points.  Additive keyword arguments (all optional
     mode: ``energy_sums[:, 0] / cells``); both are NaN where ``cells == 0``.  A sampled step is sequenced like a stored one,
     as for the traces; with both sinks each samples at the steps of its own cadence.  Not covered: phonon planes,
     domain-decomposed runs, rectangular or non-power-of-two blocks.  The default ``coarse_out=None`` runs exactly as before.
+``rates_out``, ``rates_regions``, ``rates_every``
+    Collision rate traces - where the quasiparticles go: with a dict as ``rates_out`` the four per-bin collision terms
+    (``channels`` = scattering_in, scattering_out, recombination, pair_breaking, each >= 0 in units of dn_i/dt; the header
+    of ``qp_collision_rates`` has the formulas) are evaluated on the device from the state and the phonons at t = 0, every
+    ``rates_every``-th step and the last step, summed over up to 8 named regions (``rates_regions``, as ``trace_regions``),
+    kept there, and fetched once when the run ends.  ``rates_out`` is cleared at entry and filled on normal return with
+    ``times`` [S], ``regions``, ``cells``, ``energy_bins``, ``channels``, ``rates`` [S, R, 4, NE] and ``number_rates``
+    [S, R, 4] = dx^2 dE sum_i rates.  A sampled step is sequenced like a stored one and sees the state and the phonons
+    after its closing half-step, with the run's ``enable_recombination`` / ``enable_scattering`` (a disabled process gives
+    exact zeros).  Served: uniform and non-uniform gaps, ensembles and their sweeps, 2 to 64 energy bins.  Refused with a
+    ``ValueError``: scalar mode, both processes off, more than 64 energy bins (also with ``collision_wide_bins``).  Not
+    covered: rates per phonon bin.  The default ``rates_out=None`` runs exactly as before.
 
 Table builders and helpers the reference exports from ``qpsim.solver`` are re-exported here under
 the same names.
@@ -351,28 +363,107 @@ class _TracePlan:
                 f"{SAMPLE_BUFFER_LIMIT >> 20} MiB; use a larger trace_every.")
 
 
-def _trace_plan(mask: np.ndarray, tracing: bool, trace_regions, trace_every):
+def _trace_plan(mask: np.ndarray, tracing: bool, trace_regions, trace_every, kind: str = "trace", plan=_TracePlan):
     """The ``_TracePlan`` of a run, None when traces are off (``tracing``: a sink was given).  ``ValueError`` naming the
-    argument for ``trace_every`` < 1, regions without a sink, not 1 ... 8 regions, a region of another shape than the mask."""
+    argument for ``trace_every`` < 1, regions without a sink, not 1 ... 8 regions, a region of another shape than the mask.
+    The collision rate traces take their regions by the same rules (``kind="rates"``, ``plan=_RatesPlan``)."""
     if isinstance(trace_every, bool) or not isinstance(trace_every, (int, np.integer)) or trace_every < 1:
-        raise ValueError(f"trace_every must be an integer >= 1, got {trace_every!r}.")
+        raise ValueError(f"{kind}_every must be an integer >= 1, got {trace_every!r}.")
     if not tracing:
         if trace_regions is not None:
-            raise ValueError("trace_regions needs trace_out: without a sink no trace is taken.")
+            raise ValueError(f"{kind}_regions needs {kind}_out: without a sink no trace is taken.")
         return None
     if trace_regions is None:
         trace_regions = {"all": mask}
     if not isinstance(trace_regions, dict) or not 1 <= len(trace_regions) <= 8:
-        raise ValueError("trace_regions must map 1 to 8 region names to boolean arrays"
+        raise ValueError(f"{kind}_regions must map 1 to 8 region names to boolean arrays"
                          + (f", got {len(trace_regions)} regions." if isinstance(trace_regions, dict) else "."))
     names, regions = [], []
     for name, region in trace_regions.items():
         region = np.asarray(region)
         if region.shape != mask.shape:
-            raise ValueError(f"trace_regions['{name}'] has shape {region.shape}; expected the mask's shape {mask.shape}.")
+            raise ValueError(f"{kind}_regions['{name}'] has shape {region.shape}; expected the mask's shape {mask.shape}.")
         names.append(str(name))
         regions.append(region.astype(bool))
-    return _TracePlan(names, regions, [int(np.sum(r & mask)) for r in regions], int(trace_every))
+    return plan(names, regions, [int(np.sum(r & mask)) for r in regions], int(trace_every))
+
+
+RATE_CHANNELS = ("scattering_in", "scattering_out", "recombination", "pair_breaking")
+
+
+class _RatesReduce:
+    """The ``reduce`` of a rate sampler.  The samplers of a run are built before its tables and phonon planes exist, so the
+    run object is bound late: ``_bind_rates`` sets ``run`` once ``_LoneRun`` / ``_MembersRun`` is complete, and every
+    sample reads the run's current phonon planes, tables and process switches."""
+    run = None
+
+    def __init__(self, eng, bits, members: int):
+        self.eng, self.bits, self.members = eng, bits, members
+
+    def __call__(self, state, row) -> None:
+        run = self.run
+        en_r, en_s, _ = run.physics
+        self.eng.collision_rates(run.ctab, state, run.phonon, self.bits, self.members, run.dE, en_r, en_s, row)
+
+
+def _bind_rates(samplers, run) -> None:
+    for sampler in samplers:
+        if isinstance(sampler.reduce, _RatesReduce):
+            sampler.reduce.run = run
+
+
+class _RatesPlan:
+    """Checked collision-rate-trace arguments of a run, as ``_TracePlan``: region ``names``, their boolean arrays on the
+    full mask, the interior ``cells`` of each and ``every``."""
+
+    def __init__(self, names, regions, cells, every):
+        self.names, self.regions, self.cells, self.every = names, regions, cells, every
+
+    def row_shape(self, nfield: int) -> tuple:
+        return len(self.names), len(RATE_CHANNELS), nfield
+
+    def sampler(self, eng, mask, sched: Schedule, members: int, nfield: int) -> Sampler:
+        offset = (int(np.flatnonzero(mask.any(axis=1))[0]), int(np.flatnonzero(mask.any(axis=0))[0]))
+        return Sampler(eng, sched, self.every, members, self.row_shape(nfield),
+                       _RatesReduce(eng, eng.region_bits(self.regions, offset), members))
+
+    def result(self, times, rates: np.ndarray, E_bins, dx: float, dE) -> dict:
+        """``rates`` [S, R, 4, NE]."""
+        rates = np.ascontiguousarray(rates)
+        return {"times": list(times), "regions": list(self.names), "cells": list(self.cells),
+                "energy_bins": np.array(E_bins, dtype=float), "channels": list(RATE_CHANNELS), "rates": rates,
+                "number_rates": dx * dx * dE * np.sum(rates, axis=-1)}
+
+    def too_large(self, nbytes: int, rows: int, members: int, nfield: int) -> str:
+        return (f"rates_every={self.every} gives a rate buffer of {nbytes / 2 ** 20:.0f} MiB ({rows} samples x "
+                f"{members} members x {len(self.names)} regions x {len(RATE_CHANNELS)} channels x {nfield} bins x 8 B), "
+                f"above the limit of {SAMPLE_BUFFER_LIMIT >> 20} MiB; use a larger rates_every.")
+
+
+def _rates_plan(mask: np.ndarray, wanted: bool, rates_regions, rates_every, run_args):
+    """The ``_RatesPlan`` of a run, None when rate traces are off (``wanted``: a sink was given).  ``ValueError`` naming the
+    argument for what ``_trace_plan`` refuses and, with a sink, for a run the kernel does not serve: scalar mode, no
+    collision process, a ``num_energy_bins`` / phonon grid outside ``qp_collision_rates_available``.  ``run_args``: the
+    keyword arguments of the run (``energy_gap``, the two switches and the energy grid are read)."""
+    plan = _trace_plan(mask, wanted, rates_regions, rates_every, "rates", _RatesPlan)
+    if plan is None:
+        return None
+    a = run_args
+    if not a["energy_gap"] > 0.0:
+        raise ValueError("rates_out needs an energy-resolved run (energy_gap > 0): scalar mode has no collision terms.")
+    if not (a["enable_recombination"] or a["enable_scattering"]):
+        raise ValueError("rates_out needs enable_recombination or enable_scattering: with both off there is no rate.")
+    from . import _hip
+    ne = int(a["num_energy_bins"])
+    nw = 0
+    if 2 <= ne <= 64:         # the phonon grid of this energy grid (host only)
+        E_bins, _ = build_energy_grid(a["energy_gap"], a["energy_min_factor"], a["energy_max_factor"], ne)
+        nw = int(_build_phonon_frequency_map(E_bins)[0].size)
+    if not _hip.load().qp_collision_rates_available(ne, nw):
+        raise ValueError(f"rates_out: num_energy_bins={ne}" + (f" with {nw} phonon bins" if nw else "") + " is outside the "
+                         "rate kernel's range (2 to 64 energy bins, at most 191 phonon bins; collision_wide_bins does not "
+                         "extend it).")
+    return plan
 
 
 class _CoarsePlan:
@@ -447,11 +538,13 @@ def _check_sample_buffer(plan, sched: Schedule, members: int, nfield: int) -> No
         raise ValueError(plan.too_large(nbytes, sched.rows(plan.every), members, nfield))
 
 
-def _sampling_plans(mask, trace_out, trace_regions, trace_every, coarse_out, coarse_bin, coarse_every) -> list:
-    """The active ``(plan, sink)`` pairs of a run, the trace before the coarse frames; all six arguments are checked before
-    a sink is cleared."""
+def _sampling_plans(mask, trace_out, trace_regions, trace_every, coarse_out, coarse_bin, coarse_every, rates_out=None,
+                    rates_regions=None, rates_every=1, run_args=None) -> list:
+    """The active ``(plan, sink)`` pairs of a run: trace, coarse frames, collision rates, in that order; all arguments are
+    checked before a sink is cleared.  ``run_args``: the keyword arguments of the run, read by ``_rates_plan``."""
     kinds = ((_trace_plan(mask, trace_out is not None, trace_regions, trace_every), trace_out),
-             (_coarse_plan(mask, coarse_out is not None, coarse_bin, coarse_every), coarse_out))
+             (_coarse_plan(mask, coarse_out is not None, coarse_bin, coarse_every), coarse_out),
+             (_rates_plan(mask, rates_out is not None, rates_regions, rates_every, run_args), rates_out))
     active = [(plan, sink) for plan, sink in kinds if plan is not None]
     for _, sink in active:
         sink.clear()
@@ -682,17 +775,25 @@ def run_2d_crank_nicolson(
     coarse_out: dict[str, Any] | None = None,
     coarse_bin: int = 8,
     coarse_every: int = 1,
+    rates_out: dict[str, Any] | None = None,
+    rates_regions: dict[str, np.ndarray] | None = None,
+    rates_every: int = 1,
 ):
     """Run the 2-D Crank-Nicolson diffusion (+ local collisions) time loop on the GPU.
 
     Returns ``(times, frames, mass, color_limits, energy_frames_or_None, energy_bins_or_None)`` exactly
     as the reference does; ``phonon_history_out`` is cleared and filled the same way, and so is ``trace_out`` (module
-    docstring) when time traces are wanted, and ``coarse_out`` when coarse frames are.
+    docstring) when time traces are wanted, ``coarse_out`` when coarse frames are, and ``rates_out`` when collision rate
+    traces are.
     """
     mask, initial_field, store_every, n, tau_s_eff, tau_r_eff = _checked_run_arguments(
         mask, initial_field, diffusion_coefficient, dt, total_time, store_every, enable_diffusion, enable_recombination,
         enable_scattering, tau_0, tau_s, tau_r, external_generation, phonon_history_out)
-    sampling = _sampling_plans(mask, trace_out, trace_regions, trace_every, coarse_out, coarse_bin, coarse_every)
+    sampling = _sampling_plans(mask, trace_out, trace_regions, trace_every, coarse_out, coarse_bin, coarse_every, rates_out,
+                               rates_regions, rates_every,
+                               dict(energy_gap=energy_gap, enable_recombination=enable_recombination,
+                                    enable_scattering=enable_scattering, num_energy_bins=num_energy_bins,
+                                    energy_min_factor=energy_min_factor, energy_max_factor=energy_max_factor))
     device_expr.reset_run_stats()
 
     # Device grid = bounding box of the mask.  Interior cells keep their argwhere (row-major) order under the crop, so
@@ -746,6 +847,7 @@ def run_2d_crank_nicolson(
     run.generation = _Generation(external_generation, mask, E_bins, on_device=generation_on_device)
     run.verdict = _guard_rule(eng, mask, E_bins, enforce_pauli, pauli_warn_threshold, pauli_error_threshold)
     run.samplers = samplers
+    _bind_rates(samplers, run)
 
     collisions = bool(enable_recombination or enable_scattering)
     energy_loop(run, sched, diffuser, collisions=collisions,
