@@ -470,6 +470,48 @@ int qp_collision_rates(const qp_collision_tables* t, const uint8_t* region_bits,
                        int enable_scattering, void* workspace, double* out, void* stream);
 
 /*
+ * Phonon rate traces (no reference counterpart on its time loop; the terms are those of solver.py:750-788).  Per cell and
+ * phonon bin w, with q = rho * max(1 - n / max(rho, 1e-30), 0) and N_w the phonon occupation, four base sums
+ *   E_w = dE sum n_i ks0[i][j] q_j   over the pairs with E_i > E_j and idx_diff[i][j] == w
+ *   A_w = the same sum               over the pairs with E_i < E_j
+ *   R_w = dE sum n_i kr0[i][j] n_j   over all (i, j), both orders and the diagonal, with idx_sum[i][j] == w
+ *   B_w = dE sum q_i kr0[i][j] q_j   over the same pairs
+ * (the phonon update is dN_w/dt = (E_w + R_w)(1 + N_w) - (A_w + B_w) N_w) and four non-negative channels in units of dN_w/dt:
+ *   0 scattering_emission       E_w (1 + N_w)
+ *   1 scattering_absorption     A_w N_w
+ *   2 recombination_emission    R_w (1 + N_w)
+ *   3 pair_breaking_absorption  B_w N_w
+ * out[m][r][ch][w] = sum of channel ch over the cells c of member m with bit r of region_bits[c] set (region_bits as in
+ * qp_region_sums and qp_collision_rates).  Every entry of out[members][nregion][4][nw] is written; the channels of a
+ * disabled process (or of a NULL kr0 / ks0), of a bin no pair feeds and of a region without cells are exactly 0.0.
+ * state[ne][members * ncell_member] and phonon[nw][members * ncell_member] are only read, and not at all in a group of
+ * cells without a region bit (8, 4 or 2 consecutive cells, depending on nregion and nw); a cell without a bit inside
+ * a group that is loaded is skipped as a whole: NaN outside every region reaches no sum.  Of the tables the call reads kr0, ks0, rho, idx_diff, idx_sum, sign and cls / nclass as
+ * qp_collision_rates does, under the same symmetry condition (the caller checks), and requires diag_bin / anti_bin to be
+ * non-NULL without reading them: they are the host's word that idx_diff depends on |i - j| alone, idx_sum on i + j alone,
+ * and that distinct (anti)diagonals have distinct bins, which is what makes the per-bin sums race-free without atomics (a bin
+ * shared by a diagonal and an anti-diagonal is fine: the four sums are separate arrays).  Unstructured maps return
+ * QP_ERR_INVALID_ARGUMENT.  The route flags and the one-pass images are ignored.
+ * Association: a pair term is (x_i * K) * y_j with (x, y) = (n, q), (n, n), (q, q), added to its bin's sum in the order
+ * j = 0 ... ne-1 (the compiler may fuse the last product into the addition); a channel is (dE * sum) * (1 + N_w) or
+ * (dE * sum) * N_w as rounded products.
+ * Two launches, no atomics: the partition is that of qp_collision_rates - a block of 4 waves owns one (chunk, member) of
+ * QP_RATES_CHUNK consecutive cells, wave w its cells [256 w, 256 w + 256) in index order, lane <-> energy bin while the pairs
+ * are formed and lane <-> phonon bin (up to three per lane) when the channels are added; the waves combine through LDS in
+ * wave order; the second launch adds the partials of each (member, region, channel, bin) in chunk order.  Equal inputs give
+ * bitwise equal outputs, and member m of a batch gives the bits of a lone call on its planes whatever the parity of
+ * ncell_member.
+ * workspace: qp_phonon_rates_workspace_bytes = members * ceil(ncell_member / 1024) * nregion * 4 * nw * 8 bytes (0 for sizes
+ * the call refuses).  QP_ERR_UNSUPPORTED where qp_phonon_rates_available(ne, nw) is 0 (it is 1 for 2 <= ne <= 64 and
+ * 1 <= nw <= 191, and answers without a GPU) or nregion is outside 1 ... 8.
+ */
+int qp_phonon_rates_available(int32_t ne, int32_t nw);
+size_t qp_phonon_rates_workspace_bytes(int32_t nw, int64_t ncell_member, int64_t members, int32_t nregion);
+int qp_phonon_rates(const qp_collision_tables* t, const uint8_t* region_bits, int64_t ncell_member, int64_t members,
+                    int32_t nregion, const double* state, const double* phonon, double dE, int enable_recombination,
+                    int enable_scattering, void* workspace, double* out, void* stream);
+
+/*
  * Block sums (coarse frames; stands in for the frame stores of solver.py:1479-1494, reduced over bin x bin blocks).
  * state[nfield][members][ny * nx] is the layout of the time loop, flags[ny * nx] the flag plane of ONE member grid (only
  * QP_FLAG_ACTIVE is read).  bin = 2, 4, 8, 16, 32 or 64 is the block edge; blocks are aligned to the origin of the full

@@ -1214,6 +1214,28 @@ class Engine:
                                                _ptr(state), _ptr(phonon), float(dE), int(bool(en_r)), int(bool(en_s)),
                                                _ptr(ws), _ptr(out_row), self.stream), "qp_collision_rates")
 
+    def phonon_rates(self, tables, state, phonon, bits, members: int, dE: float, en_r, en_s, out_row) -> None:
+        """out_row[m][r][ch][w] = sum over the cells of region r of channel ch (emission by scattering, absorption by
+        scattering, emission by recombination, absorption by pair breaking) of phonon bin w (``qp_phonon_rates``), ``state``
+        [NE][member][cell] and ``phonon`` [NW][member][cell] only read, ``out_row`` one [members, regions, 4, NW] row of a
+        caller-owned device buffer.  Enqueues two kernels and nothing else.  The kernel adds the pairs of a bin without
+        atomics, which needs the |i - j| / i + j structure of the bin maps and symmetric tables: a table set without
+        ``diag_bin`` (forced to ``"wave_unstructured"``) or without symmetry is refused here, on the host."""
+        members, nregion, ne, nw = int(members), int(out_row.shape[-3]), int(tables["ne"]), int(tables["nw"])
+        if tables["diag_bin"] is None:
+            raise ValueError("phonon_rates: the bin maps must have the |i - j| / i + j structure (diag_bin); unstructured "
+                             "maps are not served")
+        if not tables["symmetric"]:
+            raise ValueError("phonon_rates: kr0 / ks0 / idx_diff / idx_sum must be symmetric and sign antisymmetric")
+        if (state.numel() != ne * members * self.ncell or phonon.numel() != nw * members * self.ncell
+                or tuple(out_row.shape[-2:]) != (4, nw) or not out_row.is_contiguous()):
+            raise ValueError("phonon_rates: out_row must be a contiguous [members, regions, 4, NW] row matching the planes")
+        nbytes = int(self.lib.qp_phonon_rates_workspace_bytes(nw, self.ncell, members, nregion))
+        ws = self.scratch("phonon_rates", max((nbytes + 7) // 8, 1))
+        _hip.check(self.lib.qp_phonon_rates(C.byref(tables["struct"]), _ptr(bits), self.ncell, members, nregion,
+                                            _ptr(state), _ptr(phonon), float(dE), int(bool(en_r)), int(bool(en_s)),
+                                            _ptr(ws), _ptr(out_row), self.stream), "qp_phonon_rates")
+
     def block_sums(self, state, members: int, bin: int, oy: int, ox: int, out_row) -> None:
         """out_row[m][f][cy][cx] = sum of state[f][m][cell] over the active cells of one ``bin`` x ``bin`` block
         (``qp_block_sums``; ``(oy, ox)`` as ``coarse_layout`` gives them), ``state`` laid out [field][member][cell] and

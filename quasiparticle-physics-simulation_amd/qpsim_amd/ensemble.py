@@ -32,6 +32,9 @@ wherever its state is (the conditions above), whatever the parity of the cell co
 Collision rate traces (``rates_out=[]`` of the ensemble call, ``rates_regions`` / ``rates_every`` in the common arguments):
 one ``qp_collision_rates`` call per sample serves all members of a batch, with a sweep every member through its own tables.
 A member's rates are bit-equal to its lone run's wherever its state and phonons are, whatever the parity of the cell count.
+
+Phonon rate traces (``phonon_rates_out=[]`` of the ensemble call, ``phonon_rates_regions`` / ``phonon_rates_every`` in the
+common arguments): one ``qp_phonon_rates`` call per sample, under the same rules and with the same bit-equality.
 """
 from __future__ import annotations
 
@@ -156,7 +159,7 @@ def _bytes_per_member(kw: dict, plans=()) -> float:
 def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = None, errors: str = "raise",
                                    max_members_per_batch: int | None = None, process_group=None,
                                    trace_out: list | None = None, coarse_out: list | None = None,
-                                   rates_out: list | None = None, **common) -> list:
+                                   rates_out: list | None = None, phonon_rates_out: list | None = None, **common) -> list:
     """Run ``len(members)`` independent problems batched on the device.
 
     ``common`` takes the keyword arguments of ``run_2d_crank_nicolson``; ``members[m]`` overrides only the keys of
@@ -182,11 +185,13 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
     a failed member); one block reduction launch per sample serves all members of a batch.
     Collision rate traces: ``rates_regions`` / ``rates_every`` are shared keys of ``common`` and the sink is the list
     ``rates_out`` of this call, handled exactly as ``trace_out`` is; one ``qp_collision_rates`` call per sample serves all
-    members of a batch, with a sweep each member through its own tables."""
+    members of a batch, with a sweep each member through its own tables.
+    Phonon rate traces: ``phonon_rates_regions`` / ``phonon_rates_every`` are shared keys of ``common`` and the sink is the
+    list ``phonon_rates_out`` of this call, handled exactly as ``rates_out`` is (one ``qp_phonon_rates`` call per sample)."""
     if errors not in ("raise", "return"):
         raise ValueError("errors must be 'raise' or 'return'")
     kws = member_arguments(list(members), common, sweep)
-    for sink in (trace_out, coarse_out, rates_out):
+    for sink in (trace_out, coarse_out, rates_out, phonon_rates_out):
         if sink is not None:
             sink.clear()
     # per kind of sampler that is on (plan, sink of this call, {member: what its lone run's sink would receive})
@@ -195,7 +200,8 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
         a = kws[0]
         sampling = [(plan, sink, {}) for plan, sink in S._sampling_plans(
             np.asarray(a["mask"], dtype=bool), trace_out, a["trace_regions"], a["trace_every"], coarse_out, a["coarse_bin"],
-            a["coarse_every"], rates_out, a["rates_regions"], a["rates_every"], a)]
+            a["coarse_every"], rates_out, a["rates_regions"], a["rates_every"], a, phonon_rates_out,
+            a["phonon_rates_regions"], a["phonon_rates_every"])]
     _STATS.clear()
     _STATS.update(batches=0, pair_passes=0, guarded_calls=0)
     device_expr.reset_run_stats()

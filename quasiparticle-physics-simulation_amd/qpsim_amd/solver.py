@@ -62,7 +62,20 @@ and only crosses PCIe at store points.  Additive keyword arguments (all optional
     after its closing half-step, with the run's ``enable_recombination`` / ``enable_scattering`` (a disabled process gives
     exact zeros).  Served: uniform and non-uniform gaps, ensembles and their sweeps, 2 to 64 energy bins.  Refused with a
     ``ValueError``: scalar mode, both processes off, more than 64 energy bins (also with ``collision_wide_bins``).  Not
-    covered: rates per phonon bin.  The default ``rates_out=None`` runs exactly as before.
+    covered here: rates per phonon bin, which ``phonon_rates_out`` gives.  The default ``rates_out=None`` runs exactly as
+    before.
+``phonon_rates_out``, ``phonon_rates_regions``, ``phonon_rates_every``
+    Phonon rate traces - what the quasiparticles emit and what is absorbed again, per phonon bin: with a dict as
+    ``phonon_rates_out`` the four terms of the phonon equation (``channels`` = scattering_emission, scattering_absorption,
+    recombination_emission, pair_breaking_absorption, each >= 0 in units of dN_w/dt; the header of ``qp_phonon_rates`` has
+    the formulas) are evaluated on the device from the state and the phonons at t = 0, every ``phonon_rates_every``-th step
+    and the last step, summed over up to 8 named regions (``phonon_rates_regions``, as ``trace_regions``), kept there, and
+    fetched once when the run ends.  The sink is cleared at entry and filled on normal return with ``times`` [S],
+    ``regions``, ``cells``, ``channels``, ``phonon_energy_bins`` [NW], ``rates`` [S, R, 4, NW] and ``integrated_rates``
+    [S, R, 4] = dx^2 sum_w width_w rates with the integration widths of the phonon frames.  The rates are defined whether
+    or not the run updates its phonons (frozen phonons: what the bath receives).  Sequencing, process switches, what is
+    served and what is refused are those of ``rates_out``.  Not covered: unstructured phonon-bin maps, domain-decomposed
+    runs, region sums of the phonon occupations themselves.  The default ``phonon_rates_out=None`` runs exactly as before.
 
 Table builders and helpers the reference exports from ``qpsim.solver`` are re-exported here under
 the same names.
@@ -440,6 +453,28 @@ class _RatesPlan:
                 f"above the limit of {SAMPLE_BUFFER_LIMIT >> 20} MiB; use a larger rates_every.")
 
 
+def _rate_trace_grid(run_args, sink: str, available):
+    """(omega_bins, dE) of the phonon grid of a run whose sink ``sink`` (``"rates_out"``, ``"phonon_rates_out"``) is on, on
+    the host.  ``ValueError`` naming the sink for a run its kernel does not serve: scalar mode, no collision process, a
+    ``num_energy_bins`` / phonon grid for which ``available(ne, nw)`` is 0."""
+    a = run_args
+    if not a["energy_gap"] > 0.0:
+        raise ValueError(f"{sink} needs an energy-resolved run (energy_gap > 0): scalar mode has no collision terms.")
+    if not (a["enable_recombination"] or a["enable_scattering"]):
+        raise ValueError(f"{sink} needs enable_recombination or enable_scattering: with both off there is no rate.")
+    ne = int(a["num_energy_bins"])
+    nw, omega_bins, dE = 0, None, None
+    if 2 <= ne <= 64:         # the phonon grid of this energy grid (host only)
+        E_bins, dE = build_energy_grid(a["energy_gap"], a["energy_min_factor"], a["energy_max_factor"], ne)
+        omega_bins = _build_phonon_frequency_map(E_bins)[0]
+        nw = int(omega_bins.size)
+    if not available(ne, nw):
+        raise ValueError(f"{sink}: num_energy_bins={ne}" + (f" with {nw} phonon bins" if nw else "") + " is outside the "
+                         "rate kernel's range (2 to 64 energy bins, at most 191 phonon bins; collision_wide_bins does not "
+                         "extend it).")
+    return omega_bins, dE
+
+
 def _rates_plan(mask: np.ndarray, wanted: bool, rates_regions, rates_every, run_args):
     """The ``_RatesPlan`` of a run, None when rate traces are off (``wanted``: a sink was given).  ``ValueError`` naming the
     argument for what ``_trace_plan`` refuses and, with a sink, for a run the kernel does not serve: scalar mode, no
@@ -448,21 +483,64 @@ def _rates_plan(mask: np.ndarray, wanted: bool, rates_regions, rates_every, run_
     plan = _trace_plan(mask, wanted, rates_regions, rates_every, "rates", _RatesPlan)
     if plan is None:
         return None
-    a = run_args
-    if not a["energy_gap"] > 0.0:
-        raise ValueError("rates_out needs an energy-resolved run (energy_gap > 0): scalar mode has no collision terms.")
-    if not (a["enable_recombination"] or a["enable_scattering"]):
-        raise ValueError("rates_out needs enable_recombination or enable_scattering: with both off there is no rate.")
     from . import _hip
-    ne = int(a["num_energy_bins"])
+    _rate_trace_grid(run_args, "rates_out", _hip.load().qp_collision_rates_available)
+    return plan
+
+
+PHONON_RATE_CHANNELS = ("scattering_emission", "scattering_absorption", "recombination_emission", "pair_breaking_absorption")
+
+
+class _PhononRatesReduce(_RatesReduce):
+    """The ``reduce`` of a phonon rate sampler: bound late as ``_RatesReduce`` is, another kernel on the same planes."""
+
+    def __call__(self, state, row) -> None:
+        run = self.run
+        en_r, en_s, _ = run.physics
+        self.eng.phonon_rates(run.ctab, state, run.phonon, self.bits, self.members, run.dE, en_r, en_s, row)
+
+
+class _PhononRatesPlan:
+    """Checked phonon-rate-trace arguments of a run, as ``_RatesPlan``; a row holds phonon bins, not energy planes, so the
+    plan also carries the phonon grid of the run's energy grid: ``omega_bins`` [NW], ``nw`` and the integration ``widths``
+    of the phonon frames (set by ``_phonon_rates_plan``)."""
+    omega_bins = widths = None
     nw = 0
-    if 2 <= ne <= 64:         # the phonon grid of this energy grid (host only)
-        E_bins, _ = build_energy_grid(a["energy_gap"], a["energy_min_factor"], a["energy_max_factor"], ne)
-        nw = int(_build_phonon_frequency_map(E_bins)[0].size)
-    if not _hip.load().qp_collision_rates_available(ne, nw):
-        raise ValueError(f"rates_out: num_energy_bins={ne}" + (f" with {nw} phonon bins" if nw else "") + " is outside the "
-                         "rate kernel's range (2 to 64 energy bins, at most 191 phonon bins; collision_wide_bins does not "
-                         "extend it).")
+
+    def __init__(self, names, regions, cells, every):
+        self.names, self.regions, self.cells, self.every = names, regions, cells, every
+
+    def row_shape(self, nfield: int) -> tuple:
+        return len(self.names), len(PHONON_RATE_CHANNELS), self.nw
+
+    def sampler(self, eng, mask, sched: Schedule, members: int, nfield: int) -> Sampler:
+        offset = (int(np.flatnonzero(mask.any(axis=1))[0]), int(np.flatnonzero(mask.any(axis=0))[0]))
+        return Sampler(eng, sched, self.every, members, self.row_shape(nfield),
+                       _PhononRatesReduce(eng, eng.region_bits(self.regions, offset), members))
+
+    def result(self, times, rates: np.ndarray, E_bins, dx: float, dE) -> dict:
+        """``rates`` [S, R, 4, NW]."""
+        rates = np.ascontiguousarray(rates)
+        return {"times": list(times), "regions": list(self.names), "cells": list(self.cells),
+                "channels": list(PHONON_RATE_CHANNELS), "phonon_energy_bins": np.array(self.omega_bins, dtype=float),
+                "rates": rates, "integrated_rates": dx * dx * np.sum(self.widths * rates, axis=-1)}
+
+    def too_large(self, nbytes: int, rows: int, members: int, nfield: int) -> str:
+        return (f"phonon_rates_every={self.every} gives a rate buffer of {nbytes / 2 ** 20:.0f} MiB ({rows} samples x "
+                f"{members} members x {len(self.names)} regions x {len(PHONON_RATE_CHANNELS)} channels x {self.nw} phonon "
+                f"bins x 8 B), above the limit of {SAMPLE_BUFFER_LIMIT >> 20} MiB; use a larger phonon_rates_every.")
+
+
+def _phonon_rates_plan(mask: np.ndarray, wanted: bool, regions, every, run_args):
+    """The ``_PhononRatesPlan`` of a run, None when phonon rate traces are off; refusals as ``_rates_plan``, with
+    ``phonon_rates_*`` named and ``qp_phonon_rates_available`` asked."""
+    plan = _trace_plan(mask, wanted, regions, every, "phonon_rates", _PhononRatesPlan)
+    if plan is None:
+        return None
+    from . import _hip
+    omega_bins, dE = _rate_trace_grid(run_args, "phonon_rates_out", _hip.load().qp_phonon_rates_available)
+    plan.omega_bins, plan.nw = np.asarray(omega_bins, dtype=float), int(omega_bins.size)
+    plan.widths = integration_widths_from_centers(plan.omega_bins, fallback_width=dE)
     return plan
 
 
@@ -539,12 +617,16 @@ def _check_sample_buffer(plan, sched: Schedule, members: int, nfield: int) -> No
 
 
 def _sampling_plans(mask, trace_out, trace_regions, trace_every, coarse_out, coarse_bin, coarse_every, rates_out=None,
-                    rates_regions=None, rates_every=1, run_args=None) -> list:
-    """The active ``(plan, sink)`` pairs of a run: trace, coarse frames, collision rates, in that order; all arguments are
-    checked before a sink is cleared.  ``run_args``: the keyword arguments of the run, read by ``_rates_plan``."""
+                    rates_regions=None, rates_every=1, run_args=None, phonon_rates_out=None, phonon_rates_regions=None,
+                    phonon_rates_every=1) -> list:
+    """The active ``(plan, sink)`` pairs of a run: trace, coarse frames, collision rates, phonon rates, in that order; all
+    arguments are checked before a sink is cleared.  ``run_args``: the keyword arguments of the run, read by ``_rates_plan``
+    and ``_phonon_rates_plan``."""
     kinds = ((_trace_plan(mask, trace_out is not None, trace_regions, trace_every), trace_out),
              (_coarse_plan(mask, coarse_out is not None, coarse_bin, coarse_every), coarse_out),
-             (_rates_plan(mask, rates_out is not None, rates_regions, rates_every, run_args), rates_out))
+             (_rates_plan(mask, rates_out is not None, rates_regions, rates_every, run_args), rates_out),
+             (_phonon_rates_plan(mask, phonon_rates_out is not None, phonon_rates_regions, phonon_rates_every, run_args),
+              phonon_rates_out))
     active = [(plan, sink) for plan, sink in kinds if plan is not None]
     for _, sink in active:
         sink.clear()
@@ -778,13 +860,16 @@ def run_2d_crank_nicolson(
     rates_out: dict[str, Any] | None = None,
     rates_regions: dict[str, np.ndarray] | None = None,
     rates_every: int = 1,
+    phonon_rates_out: dict[str, Any] | None = None,
+    phonon_rates_regions: dict[str, np.ndarray] | None = None,
+    phonon_rates_every: int = 1,
 ):
     """Run the 2-D Crank-Nicolson diffusion (+ local collisions) time loop on the GPU.
 
     Returns ``(times, frames, mass, color_limits, energy_frames_or_None, energy_bins_or_None)`` exactly
     as the reference does; ``phonon_history_out`` is cleared and filled the same way, and so is ``trace_out`` (module
-    docstring) when time traces are wanted, ``coarse_out`` when coarse frames are, and ``rates_out`` when collision rate
-    traces are.
+    docstring) when time traces are wanted, ``coarse_out`` when coarse frames are, ``rates_out`` when collision rate
+    traces are, and ``phonon_rates_out`` when phonon rate traces are.
     """
     mask, initial_field, store_every, n, tau_s_eff, tau_r_eff = _checked_run_arguments(
         mask, initial_field, diffusion_coefficient, dt, total_time, store_every, enable_diffusion, enable_recombination,
@@ -793,7 +878,8 @@ def run_2d_crank_nicolson(
                                rates_regions, rates_every,
                                dict(energy_gap=energy_gap, enable_recombination=enable_recombination,
                                     enable_scattering=enable_scattering, num_energy_bins=num_energy_bins,
-                                    energy_min_factor=energy_min_factor, energy_max_factor=energy_max_factor))
+                                    energy_min_factor=energy_min_factor, energy_max_factor=energy_max_factor),
+                               phonon_rates_out, phonon_rates_regions, phonon_rates_every)
     device_expr.reset_run_stats()
 
     # Device grid = bounding box of the mask.  Interior cells keep their argwhere (row-major) order under the crop, so
