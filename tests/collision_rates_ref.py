@@ -120,6 +120,27 @@ KERNEL_CASES = [
     (64, "plain", 130, 1, 8, (1, 1), "one"),
     (64, "plain", 7, 3, 1, (1, 0), "members"),
 ]
+# Stage 2 (rates_final_kernel, phonon_rates_final_kernel) adds the chunk partials in batches of FINAL_BATCH loads and then
+# one by one: exactly one batch; a batch and a remainder with three members (the m nchunk per offset of a member with
+# nchunk >= 32); two batches and a remainder.  At most 3 regions, so that the exact sums stay around a second.  A list of
+# its own (the host-side soundness tests take seconds per case here); the GPU tests and the soundness tests of both rate
+# kernels run it beside KERNEL_CASES.
+MANY_CHUNK_CASES = [
+    (12, "plain", 32 * CHUNK, 1, 1, (1, 1), "one"),
+    (12, "plain", 37 * CHUNK + 77, 3, 3, (1, 1), "classes"),
+    (12, "merged", 69 * CHUNK + 5, 1, 3, (1, 1), "one"),
+]
+FINAL_BATCH = 32      # B of the two final kernels: chunk partials loaded before the first of them is added
+
+
+def final_rounds(ncm: int) -> tuple:
+    """(chunks, whole batches, chunks added one by one) of the stage-2 kernels for a member grid of `ncm` cells."""
+    nchunk = (ncm + CHUNK - 1) // CHUNK
+    return nchunk, nchunk // FINAL_BATCH, nchunk % FINAL_BATCH
+
+
+assert [final_rounds(c[2]) for c in MANY_CHUNK_CASES] == [(32, 1, 0), (38, 1, 6), (70, 2, 6)]
+assert all(final_rounds(c[2])[1] == 0 for c in KERNEL_CASES)
 LEVELS = [1e-9, 1e-5, 1e-2, 0.5, 0.95]
 _INPUTS: dict = {}
 

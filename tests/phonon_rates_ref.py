@@ -29,7 +29,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from collision_rates_ref import (CHUNK, KERNEL_CASES as RATE_CASES, U, bound, case_inputs, case_tables,  # noqa: F401
+from collision_rates_ref import (CHUNK, KERNEL_CASES as RATE_CASES, MANY_CHUNK_CASES, U, bound, case_inputs, case_tables,  # noqa: F401
                                  exact_sum, region_sums)
 
 CHANNELS = ("scattering_emission", "scattering_absorption", "recombination_emission", "pair_breaking_absorption")

@@ -75,7 +75,7 @@ def _case_exact(case_key):
     return case, R.channels(*args, dtype=np.float64), R.channels(*args, dtype=np.longdouble)
 
 
-@pytest.mark.parametrize("case_key", R.KERNEL_CASES, ids=lambda c: f"ne{c[0]}-{c[1]}-{c[2]}x{c[3]}-r{c[4]}-{c[6]}")
+@pytest.mark.parametrize("case_key", R.KERNEL_CASES + R.MANY_CHUNK_CASES, ids=lambda c: f"ne{c[0]}-{c[1]}-{c[2]}x{c[3]}-r{c[4]}-{c[6]}")
 def test_the_bound_is_sound_on_the_inputs_of_the_gpu_tests(case_key):
     """fp64 in the kernel's association against extended precision: every pixel value within (NE + 8) u of exact, every
     region sum of c cells (added in fp64 in index order) within (NE + 8 + c - 1) u.  Scattering conserves number: the

@@ -67,7 +67,7 @@ def _run_case(torch, lib, case_key, state=None, ph=None):
     return case, got, (struct, keep, d_state, d_ph, d_bits)
 
 
-@pytest.mark.parametrize("case_key", R.KERNEL_CASES, ids=lambda c: f"ne{c[0]}-{c[1]}-{c[2]}x{c[3]}-r{c[4]}-{c[6]}")
+@pytest.mark.parametrize("case_key", R.KERNEL_CASES + R.MANY_CHUNK_CASES, ids=lambda c: f"ne{c[0]}-{c[1]}-{c[2]}x{c[3]}-r{c[4]}-{c[6]}")
 def test_rates_against_exact_sums(torch, lib, case_key):
     ne, kind, ncm, members, nregion, (en_r, en_s), family = case_key
     case, got, (struct, keep, d_state, d_ph, d_bits) = _run_case(torch, lib, case_key)

@@ -56,7 +56,7 @@ def _run_case(torch, lib, case_key, state=None, ph=None):
     return case, got, (struct, keep, d_state, d_ph, d_bits)
 
 
-@pytest.mark.parametrize("case_key", PR.KERNEL_CASES, ids=CASE_IDS)
+@pytest.mark.parametrize("case_key", PR.KERNEL_CASES + PR.MANY_CHUNK_CASES, ids=CASE_IDS)
 def test_phonon_rates_against_exact_sums(torch, lib, case_key):
     ne, kind, ncm, members, nregion, (en_r, en_s), family = case_key
     case, got, (struct, keep, d_state, d_ph, d_bits) = _run_case(torch, lib, case_key)

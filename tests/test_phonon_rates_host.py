@@ -81,7 +81,7 @@ def test_helper_reproduces_the_oracle_phonon_update(ne, family, combo):
     assert np.all(err <= 1e-12 * want)
 
 
-@pytest.mark.parametrize("case_key", PR.KERNEL_CASES, ids=CASE_IDS)
+@pytest.mark.parametrize("case_key", PR.KERNEL_CASES + PR.MANY_CHUNK_CASES, ids=CASE_IDS)
 def test_the_bound_is_sound_on_the_inputs_of_the_gpu_tests(case_key):
     """fp64 in the kernel's association against extended precision: every pixel value within (NE + 8) u of exact, every
     region sum of c cells (added in fp64 in index order) within (NE + 8 + c - 1) u."""

@@ -1,0 +1,66 @@
+"""The constants that tests/test_gpu_reduction_rounds.py and tests/collision_rates_ref.py mirror, read out of the sources
+(no GPU): a changed cap, chunk or batch fails here instead of silently moving the GPU cases out of the regime they claim."""
+from __future__ import annotations
+
+import re
+from pathlib import Path
+
+import collision_rates_ref as R
+import test_gpu_reduction_rounds as RR
+
+ROOT = Path(__file__).resolve().parent.parent
+CSRC = ROOT / "quasiparticle-physics-simulation_amd" / "csrc"
+
+
+def _find(path: Path, pattern: str) -> list:
+    found = re.findall(pattern, path.read_text())
+    assert found, f"{pattern!r} not found in {path.name}"
+    return [int(v) for v in found]
+
+
+def test_the_mirrored_constants_equal_the_sources():
+    misc, common, header = CSRC / "qp_misc.hip", CSRC / "qp_common.h", ROOT / "include" / "qpsim_hip.h"
+    assert _find(misc, r"constexpr int kRedBlocks = (\d+);") == [RR.RED_BLOCKS]
+    assert _find(common, r"constexpr int kGuardMergeBlocks = (\d+);") == [RR.GUARD_MERGE_BLOCKS]
+    assert _find(misc, r"constexpr int kRegionChunk = (\d+);") == [RR.REGION_CHUNK]
+    assert _find(misc, r"constexpr int kRegionTile = (\d+);") == [RR.REGION_TILE]
+    assert _find(header, r"#define QP_RATES_CHUNK (\d+)") == [RR.RATES_CHUNK] == [R.CHUNK]
+    assert _find(header, r"#define QP_FLAG_ACTIVE (\d+)u") == [RR.ACTIVE]
+    for name in ("qp_collision_rates.hip", "qp_phonon_rates.hip"):
+        assert _find(CSRC / name, r"constexpr int B = (\d+);") == [RR.RATES_BATCH] == [R.FINAL_BATCH], name
+    # pauli_member_budget: 2048 blocks in all, at most kRedBlocks per member
+    assert _find(misc, r"long b = (\d+) / \(members > 0 \? members : 1\);") == [RR.MEMBER_GUARD_BUDGET]
+    assert re.search(r"return b < 1 \? 1 : \(b > kRedBlocks \? kRedBlocks : b\);", misc.read_text())
+    # grid_for: the cap appears as the test and as the value
+    assert _find(misc, r"return \(unsigned\)\(b > (\d+) \? (?:\d+) : \(b < 1 \? 1 : b\)\);") == [RR.GRID_FOR_BLOCKS]
+    assert _find(misc, r"return \(unsigned\)\(b > (?:\d+) \? (\d+) : \(b < 1 \? 1 : b\)\);") == [RR.GRID_FOR_BLOCKS]
+    # every kernel of the file runs blocks of 256 threads but the two finishes that run one wave
+    assert set(_find(misc, r"__launch_bounds__\((\d+)\)")) == {RR.THREADS, 64}
+    # partial slots of the per-field norms
+    assert _find(CSRC / "qp_diffusion_general.hip", r"const long cap = norm_out \? (\d+) : \d+;") == [RR.NORM_SLOTS]
+    rect_per = r"const long per = items < (\d+) / lanes \? items : (?:\d+) / lanes;"
+    assert _find(CSRC / "qp_adi_rect.hip", rect_per) == [RR.NORM_SLOTS]
+    # the member finish of the fused guard reads one partial per wave of 64 cells, the lone one two per block of 128
+    assert re.search(r"pauli_members_final_kernel, dim3\(\(unsigned\)members\), dim3\(256\), 0, stream, parts, ncell_member / 64,",
+                     misc.read_text())
+    assert re.search(r"\(\(long\)ncell \+ 127\) / 128 \* 2", (CSRC / "qp_collision.hip").read_text())
+
+
+def test_every_case_lies_in_the_regime_it_names():
+    """The geometry restatements at the sizes of the GPU cases, without a device."""
+    for ne, _, ncell, _ in RR.PAULI_CASES:
+        geo = RR.pauli_geometry(ne, ncell)
+        assert geo["bx"] * RR.THREADS < ncell and RR.pauli_cell(geo, ncell - 1) == RR.PAULI_REGIMES[ncell]["last"]
+    assert RR.pauli_geometry(12, 21760)["bx"] * RR.THREADS == 21760 and RR.pauli_geometry(50, 5120)["bx"] * RR.THREADS == 5120
+    for members, ne, ncm in RR.MEMBERS_CASES:
+        geo = RR.members_geometry(ne, ncm, members)
+        assert {k: geo[k] for k in RR.MEMBERS_REGIMES[(members, ncm)]} == RR.MEMBERS_REGIMES[(members, ncm)]
+    assert RR.members_geometry(7, 14848, 5)["trips"] == 1 and RR.members_geometry(7, 300, 292)["bins_per_block"] == 1
+    assert RR.members_geometry(7, 300, 293)["bins_per_block"] == 2 and RR.members_geometry(5, 130, 1025)["budget"] == 1
+    for grid, shape in RR.GUARD_GRIDS.items():
+        assert RR.merge_geometry(shape[0] * shape[1]) == RR.GUARD_REGIMES[grid]
+    assert RR.merge_geometry(32768)["per"] == 1 and RR.merge_geometry(32769)["per"] == 2
+    assert RR.REGION_NCM > RR.REGION_TILE * RR.REGION_CHUNK
+    assert [RR.absmax_geometry(n) for n in sorted(RR.ABSMAX_SIZES)] == [RR.ABSMAX_SIZES[n] for n in sorted(RR.ABSMAX_SIZES)]
+    assert RR.grid_for_trips(RR.GRID_FOR_BLOCKS * RR.THREADS) == 1 and RR.grid_for_trips(RR.PAST_ONE_TRIP) == 2
+    assert [R.final_rounds(c[2])[1] for c in R.MANY_CHUNK_CASES] == [1, 1, 2]
