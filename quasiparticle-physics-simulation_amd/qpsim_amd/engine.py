@@ -1202,17 +1202,8 @@ class Engine:
         read, ``out_row`` one [members, regions, 4, NE] row of a caller-owned device buffer.  Enqueues two kernels and
         nothing else.  The kernel reads row j of the tables for the pairs (lane, j): tables that are not symmetric are
         refused here, on the host."""
-        members, nregion, ne = int(members), int(out_row.shape[-3]), int(tables["ne"])
-        if not tables["symmetric"]:
-            raise ValueError("collision_rates: kr0 / ks0 / idx_diff / idx_sum must be symmetric and sign antisymmetric")
-        if (state.numel() != ne * members * self.ncell or phonon.numel() != int(tables["nw"]) * members * self.ncell
-                or tuple(out_row.shape[-2:]) != (4, ne) or not out_row.is_contiguous()):
-            raise ValueError("collision_rates: out_row must be a contiguous [members, regions, 4, NE] row matching the state")
-        nbytes = int(self.lib.qp_collision_rates_workspace_bytes(ne, self.ncell, members, nregion))
-        ws = self.scratch("collision_rates", max((nbytes + 7) // 8, 1))
-        _hip.check(self.lib.qp_collision_rates(C.byref(tables["struct"]), _ptr(bits), self.ncell, members, nregion,
-                                               _ptr(state), _ptr(phonon), float(dE), int(bool(en_r)), int(bool(en_s)),
-                                               _ptr(ws), _ptr(out_row), self.stream), "qp_collision_rates")
+        self._rates("collision_rates", int(tables["ne"]), "[members, regions, 4, NE] row matching the state", tables, state,
+                    phonon, bits, members, dE, en_r, en_s, out_row)
 
     def phonon_rates(self, tables, state, phonon, bits, members: int, dE: float, en_r, en_s, out_row) -> None:
         """out_row[m][r][ch][w] = sum over the cells of region r of channel ch (emission by scattering, absorption by
@@ -1221,20 +1212,26 @@ class Engine:
         caller-owned device buffer.  Enqueues two kernels and nothing else.  The kernel adds the pairs of a bin without
         atomics, which needs the |i - j| / i + j structure of the bin maps and symmetric tables: a table set without
         ``diag_bin`` (forced to ``"wave_unstructured"``) or without symmetry is refused here, on the host."""
-        members, nregion, ne, nw = int(members), int(out_row.shape[-3]), int(tables["ne"]), int(tables["nw"])
         if tables["diag_bin"] is None:
             raise ValueError("phonon_rates: the bin maps must have the |i - j| / i + j structure (diag_bin); unstructured "
                              "maps are not served")
+        self._rates("phonon_rates", int(tables["nw"]), "[members, regions, 4, NW] row matching the planes", tables, state,
+                    phonon, bits, members, dE, en_r, en_s, out_row)
+
+    def _rates(self, name: str, count: int, row: str, tables, state, phonon, bits, members, dE, en_r, en_s, out_row):
+        """``collision_rates`` / ``phonon_rates`` (``name``) from the symmetry check on: the shapes against ``count`` values
+        per region and channel (``row``: how the message describes ``out_row``), the workspace of ``qp_<name>_workspace_bytes`` in the scratch ``name``, the call."""
+        members, nregion, ne, nw = int(members), int(out_row.shape[-3]), int(tables["ne"]), int(tables["nw"])
         if not tables["symmetric"]:
-            raise ValueError("phonon_rates: kr0 / ks0 / idx_diff / idx_sum must be symmetric and sign antisymmetric")
+            raise ValueError(f"{name}: kr0 / ks0 / idx_diff / idx_sum must be symmetric and sign antisymmetric")
         if (state.numel() != ne * members * self.ncell or phonon.numel() != nw * members * self.ncell
-                or tuple(out_row.shape[-2:]) != (4, nw) or not out_row.is_contiguous()):
-            raise ValueError("phonon_rates: out_row must be a contiguous [members, regions, 4, NW] row matching the planes")
-        nbytes = int(self.lib.qp_phonon_rates_workspace_bytes(nw, self.ncell, members, nregion))
-        ws = self.scratch("phonon_rates", max((nbytes + 7) // 8, 1))
-        _hip.check(self.lib.qp_phonon_rates(C.byref(tables["struct"]), _ptr(bits), self.ncell, members, nregion,
-                                            _ptr(state), _ptr(phonon), float(dE), int(bool(en_r)), int(bool(en_s)),
-                                            _ptr(ws), _ptr(out_row), self.stream), "qp_phonon_rates")
+                or tuple(out_row.shape[-2:]) != (4, count) or not out_row.is_contiguous()):
+            raise ValueError(f"{name}: out_row must be a contiguous {row}")
+        nbytes = int(getattr(self.lib, f"qp_{name}_workspace_bytes")(count, self.ncell, members, nregion))
+        ws = self.scratch(name, max((nbytes + 7) // 8, 1))
+        _hip.check(getattr(self.lib, f"qp_{name}")(C.byref(tables["struct"]), _ptr(bits), self.ncell, members, nregion,
+                                                   _ptr(state), _ptr(phonon), float(dE), int(bool(en_r)), int(bool(en_s)),
+                                                   _ptr(ws), _ptr(out_row), self.stream), f"qp_{name}")
 
     def block_sums(self, state, members: int, bin: int, oy: int, ox: int, out_row) -> None:
         """out_row[m][f][cy][cx] = sum of state[f][m][cell] over the active cells of one ``bin`` x ``bin`` block

@@ -402,21 +402,30 @@ def _trace_plan(mask: np.ndarray, tracing: bool, trace_regions, trace_every, kin
 
 
 RATE_CHANNELS = ("scattering_in", "scattering_out", "recombination", "pair_breaking")
+PHONON_RATE_CHANNELS = ("scattering_emission", "scattering_absorption", "recombination_emission", "pair_breaking_absorption")
 
 
 class _RatesReduce:
-    """The ``reduce`` of a rate sampler.  The samplers of a run are built before its tables and phonon planes exist, so the
-    run object is bound late: ``_bind_rates`` sets ``run`` once ``_LoneRun`` / ``_MembersRun`` is complete, and every
-    sample reads the run's current phonon planes, tables and process switches."""
+    """The ``reduce`` of a rate sampler: ``method`` names the engine call (``collision_rates``, ``phonon_rates``).  The
+    samplers of a run are built before its tables and phonon planes exist, so the run object is bound late: ``_bind_rates``
+    sets ``run`` once ``_LoneRun`` / ``_MembersRun`` is complete, and every sample reads the run's current phonon planes,
+    tables and process switches."""
     run = None
 
-    def __init__(self, eng, bits, members: int):
-        self.eng, self.bits, self.members = eng, bits, members
+    def __init__(self, eng, bits, members: int, method: str = "collision_rates"):
+        self.eng, self.bits, self.members, self.method = eng, bits, members, method
 
     def __call__(self, state, row) -> None:
         run = self.run
         en_r, en_s, _ = run.physics
-        self.eng.collision_rates(run.ctab, state, run.phonon, self.bits, self.members, run.dE, en_r, en_s, row)
+        getattr(self.eng, self.method)(run.ctab, state, run.phonon, self.bits, self.members, run.dE, en_r, en_s, row)
+
+
+class _PhononRatesReduce(_RatesReduce):
+    """``_RatesReduce`` on ``Engine.phonon_rates``."""
+
+    def __init__(self, eng, bits, members: int):
+        super().__init__(eng, bits, members, "phonon_rates")
 
 
 def _bind_rates(samplers, run) -> None:
@@ -425,32 +434,66 @@ def _bind_rates(samplers, run) -> None:
             sampler.reduce.run = run
 
 
-class _RatesPlan:
-    """Checked collision-rate-trace arguments of a run, as ``_TracePlan``: region ``names``, their boolean arrays on the
-    full mask, the interior ``cells`` of each and ``every``."""
+class _RatePlan:
+    """Checked rate-trace arguments of a run, as ``_TracePlan``: region ``names``, their boolean arrays on the full mask,
+    the interior ``cells`` of each and ``every``.  A kind of rate trace states ``kind`` (the prefix of its keywords),
+    ``channels``, ``method`` (the engine call of its reduce, ``qp_<method>_available`` its size query), ``bin_word``,
+    ``bins(nfield)`` of a row and what ``extra`` adds to the result."""
 
     def __init__(self, names, regions, cells, every):
         self.names, self.regions, self.cells, self.every = names, regions, cells, every
 
     def row_shape(self, nfield: int) -> tuple:
-        return len(self.names), len(RATE_CHANNELS), nfield
+        return len(self.names), len(self.channels), self.bins(nfield)
 
     def sampler(self, eng, mask, sched: Schedule, members: int, nfield: int) -> Sampler:
         offset = (int(np.flatnonzero(mask.any(axis=1))[0]), int(np.flatnonzero(mask.any(axis=0))[0]))
         return Sampler(eng, sched, self.every, members, self.row_shape(nfield),
-                       _RatesReduce(eng, eng.region_bits(self.regions, offset), members))
+                       _RatesReduce(eng, eng.region_bits(self.regions, offset), members, self.method))
 
     def result(self, times, rates: np.ndarray, E_bins, dx: float, dE) -> dict:
-        """``rates`` [S, R, 4, NE]."""
+        """``rates`` [S, R, 4, bins]."""
         rates = np.ascontiguousarray(rates)
         return {"times": list(times), "regions": list(self.names), "cells": list(self.cells),
-                "energy_bins": np.array(E_bins, dtype=float), "channels": list(RATE_CHANNELS), "rates": rates,
-                "number_rates": dx * dx * dE * np.sum(rates, axis=-1)}
+                "channels": list(self.channels), "rates": rates, **self.extra(rates, E_bins, dx, dE)}
 
     def too_large(self, nbytes: int, rows: int, members: int, nfield: int) -> str:
-        return (f"rates_every={self.every} gives a rate buffer of {nbytes / 2 ** 20:.0f} MiB ({rows} samples x "
-                f"{members} members x {len(self.names)} regions x {len(RATE_CHANNELS)} channels x {nfield} bins x 8 B), "
-                f"above the limit of {SAMPLE_BUFFER_LIMIT >> 20} MiB; use a larger rates_every.")
+        return (f"{self.kind}_every={self.every} gives a rate buffer of {nbytes / 2 ** 20:.0f} MiB ({rows} samples x "
+                f"{members} members x {len(self.names)} regions x {len(self.channels)} channels x {self.bins(nfield)} "
+                f"{self.bin_word} x 8 B), above the limit of {SAMPLE_BUFFER_LIMIT >> 20} MiB; use a larger {self.kind}_every.")
+
+    def set_phonon_grid(self, omega_bins, dE) -> None:
+        """The phonon grid of the run's energy grid, for a plan that keeps it."""
+
+
+class _RatesPlan(_RatePlan):
+    """The collision rate traces: a row holds the energy planes."""
+    kind, channels, method, bin_word = "rates", RATE_CHANNELS, "collision_rates", "bins"
+
+    def bins(self, nfield: int) -> int:
+        return nfield
+
+    def extra(self, rates, E_bins, dx, dE) -> dict:
+        return {"energy_bins": np.array(E_bins, dtype=float), "number_rates": dx * dx * dE * np.sum(rates, axis=-1)}
+
+
+class _PhononRatesPlan(_RatePlan):
+    """The phonon rate traces: a row holds phonon bins, not energy planes, so the plan also carries the phonon grid of the
+    run's energy grid: ``omega_bins`` [NW], ``nw`` and the integration ``widths`` of the phonon frames."""
+    kind, channels, method, bin_word = "phonon_rates", PHONON_RATE_CHANNELS, "phonon_rates", "phonon bins"
+    omega_bins = widths = None
+    nw = 0
+
+    def bins(self, nfield: int) -> int:
+        return self.nw
+
+    def extra(self, rates, E_bins, dx, dE) -> dict:
+        return {"phonon_energy_bins": np.array(self.omega_bins, dtype=float),
+                "integrated_rates": dx * dx * np.sum(self.widths * rates, axis=-1)}
+
+    def set_phonon_grid(self, omega_bins, dE) -> None:
+        self.omega_bins, self.nw = np.asarray(omega_bins, dtype=float), int(omega_bins.size)
+        self.widths = integration_widths_from_centers(self.omega_bins, fallback_width=dE)
 
 
 def _rate_trace_grid(run_args, sink: str, available):
@@ -475,73 +518,25 @@ def _rate_trace_grid(run_args, sink: str, available):
     return omega_bins, dE
 
 
-def _rates_plan(mask: np.ndarray, wanted: bool, rates_regions, rates_every, run_args):
-    """The ``_RatesPlan`` of a run, None when rate traces are off (``wanted``: a sink was given).  ``ValueError`` naming the
-    argument for what ``_trace_plan`` refuses and, with a sink, for a run the kernel does not serve: scalar mode, no
-    collision process, a ``num_energy_bins`` / phonon grid outside ``qp_collision_rates_available``.  ``run_args``: the
-    keyword arguments of the run (``energy_gap``, the two switches and the energy grid are read)."""
-    plan = _trace_plan(mask, wanted, rates_regions, rates_every, "rates", _RatesPlan)
+def _rate_plan(kind, mask: np.ndarray, wanted: bool, regions, every, run_args):
+    """The plan of class ``kind`` of a run, None when its traces are off (``wanted``: a sink was given).  ``ValueError``
+    naming the argument for what ``_trace_plan`` refuses and, with a sink, for a run the kernel does not serve: scalar mode,
+    no collision process, a ``num_energy_bins`` / phonon grid outside the kernel's size query.  ``run_args``: the keyword
+    arguments of the run (``energy_gap``, the two switches and the energy grid are read)."""
+    plan = _trace_plan(mask, wanted, regions, every, kind.kind, kind)
     if plan is None:
         return None
     from . import _hip
-    _rate_trace_grid(run_args, "rates_out", _hip.load().qp_collision_rates_available)
+    plan.set_phonon_grid(*_rate_trace_grid(run_args, f"{kind.kind}_out", getattr(_hip.load(), f"qp_{kind.method}_available")))
     return plan
 
 
-PHONON_RATE_CHANNELS = ("scattering_emission", "scattering_absorption", "recombination_emission", "pair_breaking_absorption")
-
-
-class _PhononRatesReduce(_RatesReduce):
-    """The ``reduce`` of a phonon rate sampler: bound late as ``_RatesReduce`` is, another kernel on the same planes."""
-
-    def __call__(self, state, row) -> None:
-        run = self.run
-        en_r, en_s, _ = run.physics
-        self.eng.phonon_rates(run.ctab, state, run.phonon, self.bits, self.members, run.dE, en_r, en_s, row)
-
-
-class _PhononRatesPlan:
-    """Checked phonon-rate-trace arguments of a run, as ``_RatesPlan``; a row holds phonon bins, not energy planes, so the
-    plan also carries the phonon grid of the run's energy grid: ``omega_bins`` [NW], ``nw`` and the integration ``widths``
-    of the phonon frames (set by ``_phonon_rates_plan``)."""
-    omega_bins = widths = None
-    nw = 0
-
-    def __init__(self, names, regions, cells, every):
-        self.names, self.regions, self.cells, self.every = names, regions, cells, every
-
-    def row_shape(self, nfield: int) -> tuple:
-        return len(self.names), len(PHONON_RATE_CHANNELS), self.nw
-
-    def sampler(self, eng, mask, sched: Schedule, members: int, nfield: int) -> Sampler:
-        offset = (int(np.flatnonzero(mask.any(axis=1))[0]), int(np.flatnonzero(mask.any(axis=0))[0]))
-        return Sampler(eng, sched, self.every, members, self.row_shape(nfield),
-                       _PhononRatesReduce(eng, eng.region_bits(self.regions, offset), members))
-
-    def result(self, times, rates: np.ndarray, E_bins, dx: float, dE) -> dict:
-        """``rates`` [S, R, 4, NW]."""
-        rates = np.ascontiguousarray(rates)
-        return {"times": list(times), "regions": list(self.names), "cells": list(self.cells),
-                "channels": list(PHONON_RATE_CHANNELS), "phonon_energy_bins": np.array(self.omega_bins, dtype=float),
-                "rates": rates, "integrated_rates": dx * dx * np.sum(self.widths * rates, axis=-1)}
-
-    def too_large(self, nbytes: int, rows: int, members: int, nfield: int) -> str:
-        return (f"phonon_rates_every={self.every} gives a rate buffer of {nbytes / 2 ** 20:.0f} MiB ({rows} samples x "
-                f"{members} members x {len(self.names)} regions x {len(PHONON_RATE_CHANNELS)} channels x {self.nw} phonon "
-                f"bins x 8 B), above the limit of {SAMPLE_BUFFER_LIMIT >> 20} MiB; use a larger phonon_rates_every.")
+def _rates_plan(mask: np.ndarray, wanted: bool, rates_regions, rates_every, run_args):
+    return _rate_plan(_RatesPlan, mask, wanted, rates_regions, rates_every, run_args)
 
 
 def _phonon_rates_plan(mask: np.ndarray, wanted: bool, regions, every, run_args):
-    """The ``_PhononRatesPlan`` of a run, None when phonon rate traces are off; refusals as ``_rates_plan``, with
-    ``phonon_rates_*`` named and ``qp_phonon_rates_available`` asked."""
-    plan = _trace_plan(mask, wanted, regions, every, "phonon_rates", _PhononRatesPlan)
-    if plan is None:
-        return None
-    from . import _hip
-    omega_bins, dE = _rate_trace_grid(run_args, "phonon_rates_out", _hip.load().qp_phonon_rates_available)
-    plan.omega_bins, plan.nw = np.asarray(omega_bins, dtype=float), int(omega_bins.size)
-    plan.widths = integration_widths_from_centers(plan.omega_bins, fallback_width=dE)
-    return plan
+    return _rate_plan(_PhononRatesPlan, mask, wanted, regions, every, run_args)
 
 
 class _CoarsePlan:

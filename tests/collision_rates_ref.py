@@ -105,6 +105,8 @@ def region_sums(ch, region) -> np.ndarray:
 # gap classes through cls, "members" = one table set per member (member classes; members = 3).
 # ncell_member: 1; around a group of 8; the chunk edges; three chunks with a ragged last one.  Not omitted: ne = 64 with 8
 # regions, ne = 2, an odd ncm with 3 members, the three-chunk ragged case with gap classes, member classes with 3 members.
+# The last two have 2 regions (the NR = 2 instantiation of the collision kernel): within one wave, and across three chunks
+# with gap classes.
 KERNEL_CASES = [
     (2, "plain", 1, 1, 1, (1, 1), "one"),
     (2, "plain", 9, 3, 3, (1, 1), "classes"),
@@ -119,8 +121,10 @@ KERNEL_CASES = [
     (50, "plain", CHUNK + 1, 1, 1, (1, 0), "one"),
     (64, "plain", 130, 1, 8, (1, 1), "one"),
     (64, "plain", 7, 3, 1, (1, 0), "members"),
+    (12, "plain", 9, 1, 2, (1, 1), "one"),
+    (50, "merged", 2 * CHUNK + 3, 1, 2, (1, 1), "classes"),
 ]
-# Stage 2 (rates_final_kernel, phonon_rates_final_kernel) adds the chunk partials in batches of FINAL_BATCH loads and then
+# Stage 2 (rates_final_kernel, shared by both rate kernels) adds the chunk partials in batches of FINAL_BATCH loads and then
 # one by one: exactly one batch; a batch and a remainder with three members (the m nchunk per offset of a member with
 # nchunk >= 32); two batches and a remainder.  At most 3 regions, so that the exact sums stay around a second.  A list of
 # its own (the host-side soundness tests take seconds per case here); the GPU tests and the soundness tests of both rate
@@ -130,7 +134,7 @@ MANY_CHUNK_CASES = [
     (12, "plain", 37 * CHUNK + 77, 3, 3, (1, 1), "classes"),
     (12, "merged", 69 * CHUNK + 5, 1, 3, (1, 1), "one"),
 ]
-FINAL_BATCH = 32      # B of the two final kernels: chunk partials loaded before the first of them is added
+FINAL_BATCH = 32      # B of rates_final_kernel: chunk partials loaded before the first of them is added
 
 
 def final_rounds(ncm: int) -> tuple:

@@ -109,6 +109,13 @@ def test_the_bound_is_sound_on_the_inputs_of_the_gpu_tests(case_key):
         assert np.all(np.abs(a - b) <= 2 * (R.bound(ne, 1) + ne * U) * np.maximum(a, b))
 
 
+def test_the_cases_reach_every_instantiation_of_the_collision_kernel():
+    """Regions rounded up to 1, 2, 4, 8: all four, each also past one chunk (the wave-order combine and the finish)."""
+    nr = lambda nregion: 1 if nregion == 1 else 2 if nregion == 2 else 4 if nregion <= 4 else 8  # noqa: E731
+    assert {nr(c[4]) for c in R.KERNEL_CASES} == {1, 2, 4, 8}
+    assert {nr(c[4]) for c in R.KERNEL_CASES + R.MANY_CHUNK_CASES if c[2] > R.CHUNK} == {1, 2, 4, 8}
+
+
 def test_the_bound_is_sound_on_the_oracle_inputs():
     for ne in (12, 50):
         h = CE.host_setup(ne, "regimes")

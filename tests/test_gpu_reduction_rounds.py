@@ -48,7 +48,7 @@ GUARD_MERGE_BLOCKS = 512      # kGuardMergeBlocks, csrc/qp_common.h
 REGION_CHUNK = 8192           # kRegionChunk, csrc/qp_misc.hip
 REGION_TILE = 512             # kRegionTile, csrc/qp_misc.hip
 RATES_CHUNK = R.CHUNK         # QP_RATES_CHUNK, include/qpsim_hip.h
-RATES_BATCH = R.FINAL_BATCH   # B of rates_final_kernel and phonon_rates_final_kernel
+RATES_BATCH = R.FINAL_BATCH   # B of rates_final_kernel (the finish of both rate kernels)
 MEMBER_GUARD_BUDGET = 2048    # blocks in all of pauli_members_partial_kernel (pauli_member_budget)
 GRID_FOR_BLOCKS = 8192        # cap of grid_for, csrc/qp_misc.hip
 NORM_SLOTS = 1024             # partial slots of the per-field norms (stencil_combine_launch, rect_combine_launch)

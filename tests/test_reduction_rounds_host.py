@@ -26,8 +26,11 @@ def test_the_mirrored_constants_equal_the_sources():
     assert _find(misc, r"constexpr int kRegionTile = (\d+);") == [RR.REGION_TILE]
     assert _find(header, r"#define QP_RATES_CHUNK (\d+)") == [RR.RATES_CHUNK] == [R.CHUNK]
     assert _find(header, r"#define QP_FLAG_ACTIVE (\d+)u") == [RR.ACTIVE]
-    for name in ("qp_collision_rates.hip", "qp_phonon_rates.hip"):
-        assert _find(CSRC / name, r"constexpr int B = (\d+);") == [RR.RATES_BATCH] == [R.FINAL_BATCH], name
+    # the finish of both rate kernels: once in qp_collision_rates.hip, no second copy in the other unit or their header
+    assert _find(CSRC / "qp_collision_rates.hip", r"constexpr int B = (\d+);") == [RR.RATES_BATCH] == [R.FINAL_BATCH]
+    for name in ("qp_phonon_rates.hip", "qp_rates_frame.h"):
+        assert "constexpr int B" not in (CSRC / name).read_text() and "__global__ void __launch_bounds__(64)" not in (
+            CSRC / name).read_text(), name
     # pauli_member_budget: 2048 blocks in all, at most kRedBlocks per member
     assert _find(misc, r"long b = (\d+) / \(members > 0 \? members : 1\);") == [RR.MEMBER_GUARD_BUDGET]
     assert re.search(r"return b < 1 \? 1 : \(b > kRedBlocks \? kRedBlocks : b\);", misc.read_text())
