@@ -512,6 +512,45 @@ int qp_phonon_rates(const qp_collision_tables* t, const uint8_t* region_bits, in
                     int enable_scattering, void* workspace, double* out, void* stream);
 
 /*
+ * Boundary outflow (flux traces; no reference counterpart on its time loop: the terms are the boundary terms of
+ * solver.py:112-149 as the operator applies them).  A boundary face k of interior cell c = face_cell[k] carries
+ * (face_diag[k], face_src[k]) in 1/dx^2 units and adds D (-diag u_c + src) / dx^2 to du_c/dt; its outflow term is
+ *   term_k = D * (diag_k * u_c - src_k)         three roundings: the product, the difference, the product - never an fma,
+ * the bits of NumPy's D * (diag * u - src), with D = dcoef[f] or, when dfield is given, dfield[f][c] (the cell's own D, as
+ * the reference scales boundary terms).  Exactly one of dcoef / dfield is non-NULL.  The planes are state[i][m][cell] as in
+ * the time loop, f = i * members + m is the field index of the diffusion operator (dcoef[nplane * members],
+ * dfield[nplane * members][ncell_member]), and
+ *   out[m][s][i] = sum of term_k over the faces k of surface s         (positive: quasiparticles leave)
+ * for nsurface = 1 ... 64 surfaces.  The face list is grouped by surface: surface s owns the faces
+ * [surface_begin[s], surface_begin[s + 1]) (host array of nsurface + 1 offsets, ascending from 0 to nface; a surface may be
+ * empty and gives +0.0).  The chunk table cuts the list into nchunk chunks, rows of three int32 (first face, faces,
+ * surface) in ascending face order with 1 <= faces <= QP_FLUX_CHUNK and no chunk reaching outside its surface; the call
+ * reads it on the host (chunks_host, validated before any launch) and on the device (chunks_dev, the same rows - the
+ * caller's word).  face_cell, face_diag, face_src and chunks_dev are device arrays that a run uploads once; face_cell
+ * entries must lie in [0, ncell_member) (the caller's word as well: the host cannot see them).  With nface = nchunk = 0
+ * every entry of out is +0.0 and the face arrays may be NULL.
+ * Two launches, no atomics, no completion counters: a block of 4 waves owns one (chunk, field); thread t takes the faces
+ * t, t + 256, t + 512, t + 768 of the chunk (coalesced index and coefficient loads, the four gathers of u - and of D -
+ * issued together), adds its four terms in that order (a face beyond the chunk enters as +0.0 through a select), the 64
+ * lanes of a wave combine by shuffles from the upper half down, the waves through LDS as ((w0 + w1) + w2) + w3; the second
+ * launch, one wave per field, lets lane s add the chunk partials of surface s in chunk order and write out[m][s][i] (hence
+ * at most 64 surfaces).  Which thread adds which face depends on the face list alone - not on the plane, its alignment or
+ * ncell_member - so equal inputs give bitwise equal outputs, and member m of a batch gives the bits of a lone call on its
+ * planes.  Only cells on listed faces are loaded: NaN anywhere else reaches no sum.  A surface of very many chunks is added
+ * by one lane in order (a known limit: masks with millions of boundary faces).
+ * workspace: qp_boundary_flux_workspace_bytes = max(nplane * members * nchunk, 1) * 8 bytes (0 for sizes the call refuses).
+ * QP_ERR_INVALID_ARGUMENT, before any launch, for NULL pointers, nsurface outside 1 ... 64, non-positive nplane /
+ * ncell_member / members, ncell_member above 2^31 - 1, more than 65535 fields, offsets that do not ascend to nface, and a
+ * chunk that is empty, exceeds QP_FLUX_CHUNK, is out of order or crosses a surface.
+ */
+#define QP_FLUX_CHUNK 1024
+size_t qp_boundary_flux_workspace_bytes(int32_t nplane, int64_t members, int64_t nchunk);
+int qp_boundary_flux(const double* state, const double* dcoef, const double* dfield, int32_t nplane, int64_t ncell_member,
+                     int64_t members, const int32_t* face_cell, const double* face_diag, const double* face_src,
+                     int64_t nface, const int32_t* surface_begin, int32_t nsurface, const int32_t* chunks_host,
+                     const int32_t* chunks_dev, int64_t nchunk, void* workspace, double* out, void* stream);
+
+/*
  * Block sums (coarse frames; stands in for the frame stores of solver.py:1479-1494, reduced over bin x bin blocks).
  * state[nfield][members][ny * nx] is the layout of the time loop, flags[ny * nx] the flag plane of ONE member grid (only
  * QP_FLAG_ACTIVE is read).  bin = 2, 4, 8, 16, 32 or 64 is the block edge; blocks are aligned to the origin of the full

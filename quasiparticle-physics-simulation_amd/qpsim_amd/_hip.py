@@ -105,6 +105,9 @@ SIGNATURES = {
     "qp_phonon_rates_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
     "qp_phonon_rates": (C.c_int, [C.POINTER(CollisionTables), c_dp, C.c_int64, C.c_int64, C.c_int32, c_dp, c_dp,
                                   C.c_double, C.c_int, C.c_int, c_dp, c_dp, c_dp]),
+    "qp_boundary_flux_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64]),
+    "qp_boundary_flux": (C.c_int, [c_dp, c_dp, c_dp, C.c_int32, C.c_int64, C.c_int64, c_dp, c_dp, c_dp, C.c_int64, c_dp,
+                                   C.c_int32, c_dp, c_dp, C.c_int64, c_dp, c_dp, c_dp]),
     "qp_block_sums": (C.c_int, [c_dp, c_dp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                 c_dp, c_dp]),
     "qp_pauli_members_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),

@@ -166,6 +166,90 @@ def pack_region_bits(regions, grid_mask: np.ndarray, offset=(0, 0)) -> np.ndarra
     return bits
 
 
+FLUX_CHUNK = 1024          # QP_FLUX_CHUNK of include/qpsim_hip.h: faces per block of ``qp_boundary_flux``
+FLUX_SURFACES = 64         # surfaces per call: one lane of the second stage each
+
+
+@dataclass
+class BoundaryFaces:
+    """The non-reflective boundary faces of a grid, grouped by surface (``compile_boundary_faces``): surface s owns the faces
+    ``surface_begin[s] : surface_begin[s + 1]`` of the flat arrays, sorted by cell index (faces of one cell in the
+    reference's walk order up, down, left, right); ``chunks`` [nchunk, 3] = (first face, faces, surface) cuts every surface
+    into chunks of at most ``FLUX_CHUNK`` faces that never cross a surface."""
+    face_cell: np.ndarray        # [nface] int32, r * nx + c on the grid of the mask
+    face_diag: np.ndarray        # [nface] f64, 1/dx^2 units
+    face_src: np.ndarray         # [nface] f64
+    surface_begin: np.ndarray    # [nsurface + 1] int32
+    chunks: np.ndarray           # [nchunk, 3] int32
+
+    @property
+    def counts(self) -> list:
+        return [int(v) for v in np.diff(self.surface_begin)]
+
+
+def flux_chunks(surface_begin, chunk: int = FLUX_CHUNK) -> np.ndarray:
+    """The chunk table [nchunk, 3] int32 = (first face, faces, surface) of surfaces that own the faces
+    ``surface_begin[s] : surface_begin[s + 1]``: every surface cut into chunks of ``chunk`` faces, the last one shorter; an
+    empty surface has no chunk."""
+    rows = [(b, min(chunk, int(e) - b), s)
+            for s, (b0, e) in enumerate(zip(surface_begin[:-1], surface_begin[1:])) for b in range(int(b0), int(e), chunk)]
+    return np.asarray(rows, dtype=np.int32).reshape(-1, 3)
+
+
+def compile_boundary_faces(mask: np.ndarray, edges: list[EdgeSegment], edge_conditions: dict[str, BoundaryCondition],
+                           dx: float, surfaces) -> BoundaryFaces:
+    """Flat face arrays of ``surfaces`` (a sequence of lists of edge ids; surfaces may overlap) on the grid of ``mask`` (the
+    device grid: the bounding box of the run's mask, ``edges`` cropped with it).  A boundary face belongs to the edge whose
+    boundary condition ``compile_geometry`` applies to it - the last edge that lists it - and goes to every surface naming
+    that edge with the ``_face_terms`` of its condition; faces whose terms are both zero (reflective, zero-flux Neumann)
+    are dropped, so their cells are never loaded.  Host only, vectorised apart from the loops over edges and surfaces."""
+    mask = np.asarray(mask, dtype=bool)
+    ny, nx = mask.shape
+    if ny * nx > 2 ** 31 - 1:
+        raise ValueError(f"a grid of {ny} x {nx} cells is too large for boundary faces (at most 2^31 - 1 cells)")
+    owner = {d: np.full((ny, nx), -1, dtype=np.int32) for d in _DIRECTIONS}
+    terms = np.zeros((len(edges), 2))
+    for k, edge in enumerate(edges):
+        bc = edge_conditions.get(edge.edge_id)
+        if bc is None:
+            continue
+        terms[k] = _face_terms(bc, dx)
+        for d in _DIRECTIONS:
+            rc = [(f.row, f.col) for f in edge.faces if f.direction == d]
+            if rc:
+                rows, cols = np.asarray(rc, dtype=np.int64).T
+                owner[d][rows, cols] = k
+    flags = link_flags(mask)
+    link_of = {"up": FLAG_YM, "down": FLAG_YP, "left": FLAG_XM, "right": FLAG_XP}
+    cell, walk, own = [], [], []
+    for order, d in enumerate(_DIRECTIONS):
+        r, c = np.nonzero(mask & ((flags & link_of[d]) == 0) & (owner[d] >= 0))
+        cell.append(r * nx + c)
+        walk.append(np.full(r.size, order))
+        own.append(owner[d][r, c])
+    cell, walk, own = np.concatenate(cell), np.concatenate(walk), np.concatenate(own)
+    live = (terms[own, 0] != 0.0) | (terms[own, 1] != 0.0)
+    cell, walk, own = cell[live], walk[live], own[live]
+    first = np.lexsort((walk, cell))
+    cell, own = cell[first], own[first]
+    position = {}
+    for k, edge in enumerate(edges):
+        position.setdefault(edge.edge_id, []).append(k)
+    picked, begin = [], [0]
+    for ids in surfaces:
+        wanted = np.zeros(len(edges) + 1, dtype=bool)
+        for edge_id in ids:
+            wanted[position.get(edge_id, [])] = True
+        picked.append(np.flatnonzero(wanted[own]))
+        begin.append(begin[-1] + picked[-1].size)
+    if begin[-1] > 2 ** 31 - 1:
+        raise ValueError(f"{begin[-1]} boundary faces over all surfaces are too many (at most 2^31 - 1)")
+    sel = np.concatenate(picked) if picked else np.zeros(0, dtype=np.int64)
+    surface_begin = np.asarray(begin, dtype=np.int32)
+    return BoundaryFaces(cell[sel].astype(np.int32), np.ascontiguousarray(terms[own[sel], 0]),
+                         np.ascontiguousarray(terms[own[sel], 1]), surface_begin, flux_chunks(surface_begin))
+
+
 COARSE_BINS = (2, 4, 8, 16, 32, 64)      # block edges of coarse frames (``qp_block_sums``)
 
 
@@ -1245,6 +1329,45 @@ class Engine:
             raise ValueError("block_sums: out_row must be a contiguous [members, fields, cny, cnx] row matching the state")
         _hip.check(self.lib.qp_block_sums(_ptr(state), _ptr(self.d_flags), nfield, self.ny, self.nx, members, int(bin),
                                           int(oy), int(ox), _ptr(out_row), self.stream), "qp_block_sums")
+
+    def upload_boundary_faces(self, faces: BoundaryFaces) -> dict:
+        """The face arrays and the chunk table of ``faces`` on the device, next to the host tables ``qp_boundary_flux``
+        validates on every call: the one upload of a run, handed to ``boundary_flux``."""
+        if faces.face_cell.size and not (0 <= int(faces.face_cell.min()) and int(faces.face_cell.max()) < self.ncell):
+            raise ValueError("boundary faces: a cell index lies outside the engine's grid")
+        if int(faces.surface_begin[-1]) != faces.face_cell.size or not 1 <= faces.surface_begin.size - 1 <= FLUX_SURFACES:
+            raise ValueError(f"boundary faces: 1 to {FLUX_SURFACES} surfaces whose offsets end at the face count")
+        up = lambda a, dt: self.torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.device)  # noqa: E731
+        return {"cell": up(faces.face_cell, np.int32), "diag": up(faces.face_diag, np.float64),
+                "src": up(faces.face_src, np.float64), "chunks": up(faces.chunks, np.int32),
+                "chunks_host": np.ascontiguousarray(faces.chunks, dtype=np.int32),
+                "surface_begin": np.ascontiguousarray(faces.surface_begin, dtype=np.int32),
+                "nface": int(faces.face_cell.size), "nchunk": int(faces.chunks.shape[0]),
+                "nsurface": int(faces.surface_begin.size - 1)}
+
+    def boundary_flux(self, faces: dict, op: DiffusionOperator, state, members: int, out_row) -> None:
+        """out_row[m][s][i] = sum over the faces of surface s of D (diag u - src) on plane i of member m
+        (``qp_boundary_flux``): ``faces`` from ``upload_boundary_faces``, ``state`` laid out [plane][member][cell] and only
+        read, D the coefficients ``op`` already holds on the device (``dcoef`` per field or ``dfield`` per field and cell,
+        field = plane * members + member), ``out_row`` one [members, surfaces, planes] row of a caller-owned device buffer.
+        Enqueues two kernels and nothing else.  ``op`` must be a ``DiffusionOperator`` of this engine: the block plans of a
+        domain-decomposed run are not served."""
+        if not isinstance(op, DiffusionOperator) or op.engine is not self:
+            raise ValueError("boundary_flux: op must be the DiffusionOperator of this engine's grid; the blocks of a "
+                             "domain-decomposed run are not served")
+        members, nsurface, nplane = int(members), int(out_row.shape[-2]), int(out_row.shape[-1])
+        nfield = nplane * members
+        held = op.dcoef.numel() == nfield if op.dfield is None else op.dfield.numel() == nfield * self.ncell
+        if (state.numel() != nfield * self.ncell or op.nfield != nfield or not held or tuple(out_row.shape) != (members, faces["nsurface"], nplane) or not out_row.is_contiguous()):
+            raise ValueError("boundary_flux: out_row must be a contiguous [members, surfaces, planes] row matching the "
+                             "state, the faces and the operator's fields")
+        nbytes = int(self.lib.qp_boundary_flux_workspace_bytes(nplane, members, faces["nchunk"]))
+        ws = self.scratch("boundary_flux", max((nbytes + 7) // 8, 1))
+        _hip.check(self.lib.qp_boundary_flux(_ptr(state), _ptr(op.dcoef), _ptr(op.dfield), nplane, self.ncell, members,
+                                             _ptr(faces["cell"]), _ptr(faces["diag"]), _ptr(faces["src"]), faces["nface"],
+                                             faces["surface_begin"].ctypes.data, nsurface, faces["chunks_host"].ctypes.data,
+                                             _ptr(faces["chunks"]), faces["nchunk"], _ptr(ws), _ptr(out_row), self.stream),
+                   "qp_boundary_flux")
 
     def weighted_sum(self, planes, weights, ncell: int | None = None):
         """sum_k weights[k] planes[k]; ``weights`` on the host or already on the device, ``ncell`` as ``energy_integral``."""

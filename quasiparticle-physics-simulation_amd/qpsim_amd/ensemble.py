@@ -35,6 +35,11 @@ A member's rates are bit-equal to its lone run's wherever its state and phonons 
 
 Phonon rate traces (``phonon_rates_out=[]`` of the ensemble call, ``phonon_rates_regions`` / ``phonon_rates_every`` in the
 common arguments): one ``qp_phonon_rates`` call per sample, under the same rules and with the same bit-equality.
+
+Boundary outflow traces (``flux_out=[]`` of the ensemble call, ``flux_surfaces`` / ``flux_every`` in the common arguments):
+one ``qp_boundary_flux`` call per sample serves all members of a batch, member m with the coefficients of its own fields.
+Which thread adds which face depends on the face list alone, so a member's outflow is bit-equal to its lone run's wherever
+its state is, whatever the parity of the cell count.
 """
 from __future__ import annotations
 
@@ -159,7 +164,8 @@ def _bytes_per_member(kw: dict, plans=()) -> float:
 def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = None, errors: str = "raise",
                                    max_members_per_batch: int | None = None, process_group=None,
                                    trace_out: list | None = None, coarse_out: list | None = None,
-                                   rates_out: list | None = None, phonon_rates_out: list | None = None, **common) -> list:
+                                   rates_out: list | None = None, phonon_rates_out: list | None = None,
+                                   flux_out: list | None = None, **common) -> list:
     """Run ``len(members)`` independent problems batched on the device.
 
     ``common`` takes the keyword arguments of ``run_2d_crank_nicolson``; ``members[m]`` overrides only the keys of
@@ -187,7 +193,11 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
     ``rates_out`` of this call, handled exactly as ``trace_out`` is; one ``qp_collision_rates`` call per sample serves all
     members of a batch, with a sweep each member through its own tables.
     Phonon rate traces: ``phonon_rates_regions`` / ``phonon_rates_every`` are shared keys of ``common`` and the sink is the
-    list ``phonon_rates_out`` of this call, handled exactly as ``rates_out`` is (one ``qp_phonon_rates`` call per sample)."""
+    list ``phonon_rates_out`` of this call, handled exactly as ``rates_out`` is (one ``qp_phonon_rates`` call per sample).
+    Boundary outflow traces: ``flux_surfaces`` / ``flux_every`` are shared keys of ``common`` and the sink is the list
+    ``flux_out`` of this call, filled as ``trace_out`` is (one dict per member as the lone call fills its ``flux_out``, None
+    for a failed member) but cleared only once every argument has been checked; one ``qp_boundary_flux`` call per sample
+    serves all members of a batch, each with its own diffusion coefficients."""
     if errors not in ("raise", "return"):
         raise ValueError("errors must be 'raise' or 'return'")
     kws = member_arguments(list(members), common, sweep)
@@ -201,7 +211,9 @@ def run_2d_crank_nicolson_ensemble(members: list[dict], *, sweep: dict | None = 
         sampling = [(plan, sink, {}) for plan, sink in S._sampling_plans(
             np.asarray(a["mask"], dtype=bool), trace_out, a["trace_regions"], a["trace_every"], coarse_out, a["coarse_bin"],
             a["coarse_every"], rates_out, a["rates_regions"], a["rates_every"], a, phonon_rates_out,
-            a["phonon_rates_regions"], a["phonon_rates_every"])]
+            a["phonon_rates_regions"], a["phonon_rates_every"], flux_out, a["flux_surfaces"], a["flux_every"])]
+    elif flux_out is not None:
+        flux_out.clear()
     _STATS.clear()
     _STATS.update(batches=0, pair_passes=0, guarded_calls=0)
     device_expr.reset_run_stats()
@@ -451,6 +463,8 @@ def _run_energy_batch(eng, sched, out, kws, ids, errors, inits, n, flags, taus, 
         S._Generation(k["external_generation"], mask, E_bins, on_device=a["generation_on_device"]) for k in kws]
     run.ids, run.errors, run.samplers = ids, errors, samplers
     S._bind_rates(samplers, run)
+    if diffuser is not None:
+        S._bind_flux(samplers, diffuser)
     run.verdict = S._guard_rule(eng, mask, E_bins, a["enforce_pauli"], a["pauli_warn_threshold"], a["pauli_error_threshold"])
     run.quiet_below = min([v for v in (a["pauli_warn_threshold"], a["pauli_error_threshold"]) if v is not None],
                           default=float("inf"))

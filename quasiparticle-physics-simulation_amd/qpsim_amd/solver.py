@@ -76,6 +76,25 @@ and only crosses PCIe at store points.  Additive keyword arguments (all optional
     or not the run updates its phonons (frozen phonons: what the bath receives).  Sequencing, process switches, what is
     served and what is refused are those of ``rates_out``.  Not covered: unstructured phonon-bin maps, domain-decomposed
     runs, region sums of the phonon occupations themselves.  The default ``phonon_rates_out=None`` runs exactly as before.
+``flux_out``, ``flux_surfaces``, ``flux_every``
+    Boundary outflow traces - what leaves through the walls: with a dict as ``flux_out`` the diffusive loss through up to 64
+    named surfaces (``flux_surfaces``: name -> non-empty list of edge ids of ``edges``, surfaces may overlap; None: one
+    surface ``"all"`` made of every edge) is evaluated on the device from the state at t = 0, every ``flux_every``-th step
+    and the last step, kept there, and fetched once when the run ends.  A boundary face belongs to the edge whose boundary
+    condition the operator applies to it (the last edge listing it) and carries (diag, src) in 1/dx^2 units: reflective
+    (0, 0), absorbing (2, 0), dirichlet g (2, 2 g), neumann q (0, q dx), robin beta, gamma (beta dx, gamma dx); it adds
+    D (-diag u + src) / dx^2 to du/dt of its cell, D being the bin's coefficient (the cell's own D with a non-uniform gap).
+    ``outflow[s, i]`` = sum over the faces of surface s of D (diag u_i - src) is positive when quasiparticles leave and
+    negative for an injecting source; it is minus the boundary contribution to d/dt sum_p u_i dx^2.  Faces with diag = src =
+    0 are dropped on the host (their cells are never read); a surface left without faces reports +0.0.  ``flux_out`` is
+    cleared at entry and filled on normal return with ``times`` [S], ``surfaces`` (names), ``faces`` (count per surface
+    after dropping), ``energy_bins`` (None in scalar mode), ``outflow`` [S, surfaces, planes] and ``number_outflow``
+    [S, surfaces] = dE sum_i outflow (scalar mode: outflow[..., 0]), the rate at which the run's ``mass`` is lost through
+    the surface.  A sampled step is sequenced like a stored one.  Served: scalar and energy-resolved mode, both diffusion
+    schemes, uniform and non-uniform gaps, ensembles and their sweeps.  Refused with a ``ValueError``:
+    ``enable_diffusion=False`` (no operator, no boundary term).  Not covered: domain-decomposed runs (they do not pass
+    through this call; ``Engine.boundary_flux`` refuses their block plans), phonon planes (they do not diffuse), per-face
+    output, time integration on the device.  The default ``flux_out=None`` runs exactly as before.
 
 Table builders and helpers the reference exports from ``qpsim.solver`` are re-exported here under
 the same names.
@@ -88,7 +107,8 @@ from typing import Any, Callable
 import numpy as np
 
 from . import tables as _tb
-from .engine import COARSE_BINS, BoundaryAssignmentError, DiffusionOperator, Engine, coarse_layout, compile_geometry
+from .engine import (COARSE_BINS, FLUX_SURFACES, BoundaryAssignmentError, DiffusionOperator, Engine, coarse_layout,
+                     compile_boundary_faces, compile_geometry)
 from .models import (
     BoundaryCondition,
     EdgeSegment,
@@ -599,6 +619,89 @@ def _coarse_plan(mask: np.ndarray, wanted: bool, coarse_bin, coarse_every):
     return _CoarsePlan(int(coarse_bin), int(coarse_every), coarse_layout(mask, int(coarse_bin)))
 
 
+class _FluxReduce:
+    """The ``reduce`` of a flux sampler.  The samplers of a run are built before its diffuser exists, so the operator is bound
+    late, as the run of ``_RatesReduce`` is: ``_bind_flux`` sets ``op`` to the ``DiffusionOperator`` the diffuser holds, whose
+    coefficients on the device (``dcoef`` or ``dfield``) every sample reads - no second copy is uploaded."""
+    op = None
+
+    def __init__(self, eng, faces, members: int):
+        self.eng, self.faces, self.members = eng, faces, members
+
+    def __call__(self, state, row) -> None:
+        self.eng.boundary_flux(self.faces, self.op, state, self.members, row)
+
+
+def _bind_flux(samplers, diffuser) -> None:
+    for sampler in samplers:
+        if isinstance(sampler.reduce, _FluxReduce):
+            sampler.reduce.op = diffuser.op
+
+
+class _FluxPlan:
+    """Checked boundary-outflow arguments of a run: surface ``names``, the ``engine.BoundaryFaces`` of the device grid
+    (``faces``; ``counts``: faces per surface after the reflective ones are dropped) and ``every``."""
+
+    def __init__(self, names, faces, every):
+        self.names, self.faces, self.counts, self.every = names, faces, faces.counts, every
+
+    def row_shape(self, nfield: int) -> tuple:
+        return len(self.names), nfield
+
+    def sampler(self, eng, mask, sched: Schedule, members: int, nfield: int) -> Sampler:
+        return Sampler(eng, sched, self.every, members, self.row_shape(nfield),
+                       _FluxReduce(eng, eng.upload_boundary_faces(self.faces), members))
+
+    def result(self, times, outflow: np.ndarray, E_bins, dx: float, dE) -> dict:
+        """``outflow`` [S, surfaces, planes]."""
+        outflow = np.ascontiguousarray(outflow)
+        number = outflow[..., 0].copy() if E_bins is None else dE * np.sum(outflow, axis=-1)
+        return {"times": list(times), "surfaces": list(self.names), "faces": list(self.counts),
+                "energy_bins": None if E_bins is None else np.array(E_bins, dtype=float), "outflow": outflow,
+                "number_outflow": number}
+
+    def too_large(self, nbytes: int, rows: int, members: int, nfield: int) -> str:
+        return (f"flux_every={self.every} gives a flux buffer of {nbytes / 2 ** 20:.0f} MiB ({rows} samples x "
+                f"{members} members x {len(self.names)} surfaces x {nfield} planes x 8 B), above the limit of "
+                f"{SAMPLE_BUFFER_LIMIT >> 20} MiB; use a larger flux_every.")
+
+
+def _flux_plan(mask: np.ndarray, wanted: bool, flux_surfaces, flux_every, run_args):
+    """The ``_FluxPlan`` of a run, None when the outflow traces are off (``wanted``: a sink was given).  ``ValueError`` naming
+    the argument for ``flux_every`` < 1, surfaces without a sink, not 1 ... 64 surfaces, an empty surface list, an unknown
+    edge id, and a sink on a run without diffusion.  ``run_args``: the keyword arguments of the run (``edges``,
+    ``edge_conditions``, ``dx`` and ``enable_diffusion`` are read)."""
+    if isinstance(flux_every, bool) or not isinstance(flux_every, (int, np.integer)) or flux_every < 1:
+        raise ValueError(f"flux_every must be an integer >= 1, got {flux_every!r}.")
+    if not wanted:
+        if flux_surfaces is not None:
+            raise ValueError("flux_surfaces needs flux_out: without a sink no outflow is taken.")
+        return None
+    a = run_args
+    if not a.get("enable_diffusion", True):
+        raise ValueError("flux_out needs enable_diffusion: without diffusion there is no operator and no boundary term.")
+    edges = list(a["edges"])
+    if flux_surfaces is None:
+        flux_surfaces = {"all": [e.edge_id for e in edges]}
+    if not isinstance(flux_surfaces, dict) or not 1 <= len(flux_surfaces) <= FLUX_SURFACES:
+        raise ValueError(f"flux_surfaces must map 1 to {FLUX_SURFACES} surface names to lists of edge ids"
+                         + (f", got {len(flux_surfaces)} surfaces." if isinstance(flux_surfaces, dict) else "."))
+    known = {e.edge_id for e in edges}
+    names, lists = [], []
+    for name, ids in flux_surfaces.items():
+        ids = [ids] if isinstance(ids, str) else list(ids)
+        if not ids:
+            raise ValueError(f"flux_surfaces['{name}'] is empty: a surface is a non-empty list of edge ids.")
+        for edge_id in ids:
+            if edge_id not in known:
+                raise ValueError(f"flux_surfaces['{name}'] names the unknown edge id {edge_id!r}.")
+        names.append(str(name))
+        lists.append(ids)
+    dev_mask, dev_edges = _crop_to_bounding_box(mask, edges)
+    return _FluxPlan(names, compile_boundary_faces(dev_mask, dev_edges, a["edge_conditions"], float(a["dx"]), lists),
+                     int(flux_every))
+
+
 def _sample_buffer_bytes(plan, sched: Schedule, members: int, nfield: int) -> int:
     return 8 * sched.rows(plan.every) * members * int(np.prod(plan.row_shape(nfield)))
 
@@ -613,15 +716,16 @@ def _check_sample_buffer(plan, sched: Schedule, members: int, nfield: int) -> No
 
 def _sampling_plans(mask, trace_out, trace_regions, trace_every, coarse_out, coarse_bin, coarse_every, rates_out=None,
                     rates_regions=None, rates_every=1, run_args=None, phonon_rates_out=None, phonon_rates_regions=None,
-                    phonon_rates_every=1) -> list:
-    """The active ``(plan, sink)`` pairs of a run: trace, coarse frames, collision rates, phonon rates, in that order; all
-    arguments are checked before a sink is cleared.  ``run_args``: the keyword arguments of the run, read by ``_rates_plan``
-    and ``_phonon_rates_plan``."""
+                    phonon_rates_every=1, flux_out=None, flux_surfaces=None, flux_every=1) -> list:
+    """The active ``(plan, sink)`` pairs of a run: trace, coarse frames, collision rates, phonon rates, boundary outflow, in
+    that order; all arguments are checked before a sink is cleared.  ``run_args``: the keyword arguments of the run, read by
+    ``_rates_plan``, ``_phonon_rates_plan`` and ``_flux_plan``."""
     kinds = ((_trace_plan(mask, trace_out is not None, trace_regions, trace_every), trace_out),
              (_coarse_plan(mask, coarse_out is not None, coarse_bin, coarse_every), coarse_out),
              (_rates_plan(mask, rates_out is not None, rates_regions, rates_every, run_args), rates_out),
              (_phonon_rates_plan(mask, phonon_rates_out is not None, phonon_rates_regions, phonon_rates_every, run_args),
-              phonon_rates_out))
+              phonon_rates_out),
+             (_flux_plan(mask, flux_out is not None, flux_surfaces, flux_every, run_args), flux_out))
     active = [(plan, sink) for plan, sink in kinds if plan is not None]
     for _, sink in active:
         sink.clear()
@@ -858,13 +962,16 @@ def run_2d_crank_nicolson(
     phonon_rates_out: dict[str, Any] | None = None,
     phonon_rates_regions: dict[str, np.ndarray] | None = None,
     phonon_rates_every: int = 1,
+    flux_out: dict[str, Any] | None = None,
+    flux_surfaces: dict[str, list] | None = None,
+    flux_every: int = 1,
 ):
     """Run the 2-D Crank-Nicolson diffusion (+ local collisions) time loop on the GPU.
 
     Returns ``(times, frames, mass, color_limits, energy_frames_or_None, energy_bins_or_None)`` exactly
     as the reference does; ``phonon_history_out`` is cleared and filled the same way, and so is ``trace_out`` (module
     docstring) when time traces are wanted, ``coarse_out`` when coarse frames are, ``rates_out`` when collision rate
-    traces are, and ``phonon_rates_out`` when phonon rate traces are.
+    traces are, ``phonon_rates_out`` when phonon rate traces are, and ``flux_out`` when boundary outflow traces are.
     """
     mask, initial_field, store_every, n, tau_s_eff, tau_r_eff = _checked_run_arguments(
         mask, initial_field, diffusion_coefficient, dt, total_time, store_every, enable_diffusion, enable_recombination,
@@ -873,8 +980,9 @@ def run_2d_crank_nicolson(
                                rates_regions, rates_every,
                                dict(energy_gap=energy_gap, enable_recombination=enable_recombination,
                                     enable_scattering=enable_scattering, num_energy_bins=num_energy_bins,
-                                    energy_min_factor=energy_min_factor, energy_max_factor=energy_max_factor),
-                               phonon_rates_out, phonon_rates_regions, phonon_rates_every)
+                                    energy_min_factor=energy_min_factor, energy_max_factor=energy_max_factor, edges=edges,
+                                    edge_conditions=edge_conditions, dx=dx, enable_diffusion=enable_diffusion),
+                               phonon_rates_out, phonon_rates_regions, phonon_rates_every, flux_out, flux_surfaces, flux_every)
     device_expr.reset_run_stats()
 
     # Device grid = bounding box of the mask.  Interior cells keep their argwhere (row-major) order under the crop, so
@@ -929,6 +1037,8 @@ def run_2d_crank_nicolson(
     run.verdict = _guard_rule(eng, mask, E_bins, enforce_pauli, pauli_warn_threshold, pauli_error_threshold)
     run.samplers = samplers
     _bind_rates(samplers, run)
+    if diffuser is not None:
+        _bind_flux(samplers, diffuser)
 
     collisions = bool(enable_recombination or enable_scattering)
     energy_loop(run, sched, diffuser, collisions=collisions,
@@ -1111,6 +1221,8 @@ def _run_scalar(eng: Engine, sched, out: Outputs, inits, coefficients, enable_di
     u = eng.upload_packed(u_host)
     diffuser = (_Diffuser(eng, M, sched.dt, sched.rem, scheme, rtol, dcoef=[float(D) for D in coefficients])
                 if enable_diffusion else None)
+    if diffuser is not None:
+        _bind_flux(samplers, diffuser)
     out.add_host_frames(0.0, [reconstruct_field(mask, v) for v in u_host],
                         [float(np.sum(v) * out.dx * out.dx) for v in u_host])
     scalar_loop(sched, diffuser, u, out, eng, samplers)

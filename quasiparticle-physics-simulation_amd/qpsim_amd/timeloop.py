@@ -155,7 +155,8 @@ class Sampler:
     """One cadence of sampled steps over M members: at every sample ``reduce(state, out_row)`` enqueues one device
     reduction of the planes [field][member][cell] into row k of a device buffer [rows, M, *row_shape]; nothing is read back
     before ``fetch()``.  A time trace reduces with ``Engine.region_sums`` into rows (regions, fields), the coarse frames with
-    ``Engine.block_sums`` into rows (fields, cny, cnx)."""
+    ``Engine.block_sums`` into rows (fields, cny, cnx), the boundary outflow with ``Engine.boundary_flux`` into rows
+    (surfaces, fields)."""
 
     def __init__(self, eng, sched: Schedule, every: int, members: int, row_shape: tuple, reduce):
         self.sched, self.every, self.reduce = sched, every, reduce
